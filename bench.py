@@ -10,12 +10,20 @@ the aggregate; the 32 x 32 configuration shards its cells over the ranks (pysdm_
 
     python bench.py --gpus 1 --steps 200 --warmup 20
 
-One JSON line on stdout (rank 0).  The timed region (exactly `--steps` steps between barriers) is
-repeated `--reps` times and the median repetition is reported.  `roofline` prices the dominant
-kernel of the step against the HBM peak with the algorithmic bytes of SURVEY.md 8(d) (136 B per
-candidate pair, 152 B with breakup), timed live with HIP events on the library's stream;
-`cpu_baseline` times the oracle (C restatement of the reference's Numba-backend algorithm, OpenMP
-where Numba uses `prange`) on the host for a bounded sample, at 1 thread and at all cores.
+One JSON line on stdout (rank 0).  A plain run sets up, warms up, times exactly `--steps` steps
+between barriers once and prints the line; `--dump-outputs DIR` then also writes what the last
+timed step left (the arrays a caller of the path receives) as DIR/<name>.npy, float64.
+
+`--full` adds everything else the line can carry: the timed region repeated `--reps` times (3 by
+default) with the median repetition reported, the Shima-2009 experiment run whole (3600 steps),
+the multi-cell `state_digest`, and the figures that take runs of their own.  `roofline` prices
+the dominant kernel of the step against the HBM peak with the algorithmic bytes of SURVEY.md 8(d)
+(136 B per candidate pair, 152 B with breakup), timed live with HIP events on the library's
+stream; `cpu_baseline` times the oracle (C restatement of the reference's Numba-backend
+algorithm, OpenMP where Numba uses `prange`) on the host for a bounded sample, at 1 thread and at
+all cores.
+
+    python bench.py --full --gpus 1 --steps 200 --warmup 20
 """
 import argparse
 import ctypes
@@ -314,6 +322,70 @@ def phase_timing(engine):
     return {name(i).decode(): (ms[i], count[i]) for i in range(n) if count[i] > 0}
 
 
+def timed_path_outputs(runner):
+    """what a caller of the timed path holds after its last step, as host arrays: the population
+    (permutation, live length, multiplicities, extensive attributes, sorted cell starts), the
+    per-cell diagnostics and, where the super-droplets move, their cells and positions; put
+    together from the owners when sharded (collectives: every rank calls this)"""
+    from pysdm_amd import sharding
+
+    sharded = runner.shard is not None
+    snap = sharding.gather(runner) if sharded else runner.snapshot()
+    if hasattr(runner, "displacement"):
+        pop = runner.population
+        if sharded:
+            moved = sharding.gather_population(runner.shard, pop)
+        else:
+            moved = {name: pop.engine.download(getattr(pop, name))
+                     for name in ("cell_id", "cell_origin", "position_in_cell")}
+        snap.update({name: moved[name] for name in ("cell_id", "cell_origin", "position_in_cell")})
+    return snap
+
+
+DUMP_BUDGET_BYTES = 60 * 2**20  # all files together stay below 64 MB
+DUMP_SAMPLE_SEED = 20_091_111   # which positions a sampled column keeps (fixed, not per run)
+DUMP_SAMPLE_MIN = 2**16         # columns at least this long are the per-droplet ones
+DUMP_NOT_COMPUTED = ("stats_dt_min",)  # see dump_outputs
+
+
+def dump_outputs(snap, directory):
+    """writes `snap` as directory/<name>.npy in float64 (the permutation up to the live length:
+    the slots beyond it are spare).  Above the budget, every per-droplet column keeps the same
+    seeded sample of positions along its last axis (the smaller arrays are written whole).
+    `stats_dt_min` is left out: it starts as NaN and its update is a NaN-sticky minimum, as the
+    reference's (Python min(s, m)), so it holds no value the step computed.  Anything else that
+    is not finite is an error."""
+    arrays = {}
+    for name, value in snap.items():
+        if name in DUMP_NOT_COMPUTED:
+            continue
+        value = np.asarray(value)
+        if name == "idx":
+            value = value[: int(snap["length"])]
+        arrays[name] = value.astype(np.float64)
+        if not np.isfinite(arrays[name]).all():
+            sys.exit(f"bench.py: output {name} of the timed path is not finite")
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET_BYTES:
+        large = [name for name, a in arrays.items()
+                 if a.ndim >= 1 and a.shape[-1] >= DUMP_SAMPLE_MIN]
+        fixed = sum(a.nbytes for name, a in arrays.items() if name not in large)
+        per_position = sum(arrays[name].nbytes // arrays[name].shape[-1] for name in large)
+        keep = max(1, (DUMP_BUDGET_BYTES - fixed) // max(1, per_position))
+        for name in large:
+            n = arrays[name].shape[-1]
+            if keep < n:
+                rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+                positions = np.sort(rng.choice(n, size=keep, replace=False))
+                arrays[name] = np.ascontiguousarray(arrays[name][..., positions])
+        progress(f"outputs above {DUMP_BUDGET_BYTES >> 20} MiB: {keep} sampled positions of "
+                 f"{', '.join(large)}")
+    os.makedirs(directory, exist_ok=True)
+    for name, value in arrays.items():
+        np.save(os.path.join(directory, f"{name}.npy"), value)
+    progress(f"{len(arrays)} outputs written to {directory}")
+
+
 _T0 = time.perf_counter()
 
 
@@ -327,7 +399,15 @@ def main():
     parser.add_argument("--gpus", type=int, default=1)
     parser.add_argument("--steps", type=int, default=200)
     parser.add_argument("--warmup", type=int, default=20)
-    parser.add_argument("--reps", type=int, default=3)
+    parser.add_argument("--reps", type=int, default=None,
+                        help="timed repetitions, the median reported (default: 1; 3 with --full)")
+    parser.add_argument("--full", action="store_true",
+                        help="besides the headline figure: repetitions, the 3600-step Shima "
+                             "experiment, state digest, per-kernel timing and roofline, "
+                             "random-sector calibration, CPU baseline")
+    parser.add_argument("--dump-outputs", metavar="DIR", default=None,
+                        help="after the timed steps, write what the last one computed as "
+                             "DIR/<name>.npy (float64, < 64 MB in all)")
     parser.add_argument("--workload", default="shima", choices=sorted(WORKLOADS))
     parser.add_argument("--n-sd", type=int, default=None)
     parser.add_argument("--adaptive", type=int, default=None)
@@ -354,6 +434,8 @@ def main():
     parser.add_argument("--emulate-ranks", type=int, nargs="*", default=None,
                         help="with --emulate-of: only these ranks (default: all)")
     args = parser.parse_args()
+    if args.reps is None:
+        args.reps = 3 if args.full else 1
 
     from pysdm_amd import launch
 
@@ -467,16 +549,20 @@ def main():
                     # sub-step loop) or a Python callback into torch.distributed
                     "issued_by": "library (ncclAllReduce)" if shard.library_comm
                                  else "python callback (torch.distributed.all_reduce)"}
-    # multi-cell workload: digest of the global state (put together from the owners when sharded),
-    # so that runs with different --gpus can be compared: the sharded run reproduces the
+    snap = None
+    if args.dump_outputs:
+        snap = timed_path_outputs(runner)
+        if rank == 0:
+            dump_outputs(snap, args.dump_outputs)
+    # multi-cell workload (--full): digest of the global state (put together from the owners when
+    # sharded), so that runs with different --gpus can be compared: the sharded run reproduces the
     # one-process run bit for bit
     state_digest = None
-    if pop.n_cell > 1:
+    if args.full and pop.n_cell > 1:
         import hashlib
 
-        from pysdm_amd import sharding
-
-        snap = sharding.gather(runner) if runner.shard is not None else runner.snapshot()
+        if snap is None:
+            snap = timed_path_outputs(runner)
         live = snap["idx"][: int(snap["length"])]
         state_digest = hashlib.sha256(
             np.ascontiguousarray(live).tobytes()
@@ -486,10 +572,10 @@ def main():
     median_rate = statistics.median(rates)
     _, elapsed_max, pairs_total = min(reps, key=lambda r: abs(r[0] - median_rate))
 
-    # metric part (ii): the Shima-2009 experiment itself (settings.py:14-33: 3600 steps of 1 s
-    # from the initial spectrum), run once and timed by the wall clock - not extrapolated
+    # metric part (ii), --full: the Shima-2009 experiment itself (settings.py:14-33: 3600 steps of
+    # 1 s from the initial spectrum), run once and timed by the wall clock - not extrapolated
     shima_box_s = None
-    if args.workload == "shima" and not args.skip_full_experiment:
+    if args.full and args.workload == "shima" and not args.skip_full_experiment:
         box = build_workload(args.workload, engine, rank, world, args.n_sd, adaptive,
                              read_back=False)
         barrier()
@@ -504,13 +590,14 @@ def main():
         shima_box_live = box.population.live
         del box
 
-    progress("timed region done; per-kernel timing pass")
     roofline = None
     baseline = None
     sharded_run = runner.shard is not None
-    if sharded_run and rank != 0:  # every process takes part in every step of a sharded run
+    if args.full:
+        progress("timed region done; per-kernel timing pass")
+    if args.full and sharded_run and rank != 0:  # every process takes part in every step
         runner.run(args.roofline_steps)
-    if rank == 0:
+    if args.full and rank == 0:
         # ---- per-kernel durations, HIP events on the library's own stream (separate pass)
         engine.call("sdm_ctx_set_timing", 1)
         runner.read_back = True  # events are resolved per call

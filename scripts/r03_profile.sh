@@ -4,7 +4,7 @@ set -e
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 OUT=gpurun_out/r03/prof
 mkdir -p $OUT
-B="--reps 1 --no-cpu-baseline --skip-full-experiment --roofline-steps 5"
+B="--full --reps 1 --no-cpu-baseline --skip-full-experiment --roofline-steps 5"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_shima -- python3 bench.py --steps 100 --warmup 10 $B > $OUT/stats_shima.json 2> $OUT/stats_shima.err
 python tests/prof_summary.py $OUT/stats_shima 8 | tee $OUT/stats_shima.txt
 cp $(ls $OUT/stats_shima/*/*kernel_stats.csv | tail -1) $OUT/r03_kernel_stats_shima.csv

@@ -8,7 +8,7 @@ W=$1; FLAGS=$2; COUNTERS=$3
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 OUT=gpurun_out/r04/prof
 mkdir -p $OUT
-B="--workload $W --reps 1 --no-cpu-baseline --skip-full-experiment --roofline-steps 5 $FLAGS"
+B="--full --workload $W --reps 1 --no-cpu-baseline --skip-full-experiment --roofline-steps 5 $FLAGS"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$W -- python3 bench.py $B > $OUT/stats_$W.json 2> $OUT/stats_$W.err
 python tests/prof_summary.py $OUT/stats_$W 10 | tee $OUT/stats_$W.txt
 cp $(ls $OUT/stats_$W/*/*kernel_stats.csv | tail -1) $OUT/r04_kernel_stats_$W.csv

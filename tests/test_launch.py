@@ -64,8 +64,8 @@ def test_bench_with_two_self_started_ranks_reproduces_the_one_rank_state(hip_eng
     collectives of a step far below one n_sd-wide exchange"""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env.update(SDM_BENCH_DIST_BACKEND="gloo", SDM_BENCH_ALL_ON_DEVICE0="1")
-    common = ["--workload", "kinematic2d", "--n-sd", str(2**17), "--steps", "6", "--warmup", "2",
-              "--reps", "2", "--no-cpu-baseline", "--roofline-steps", "2"]
+    common = ["--full", "--workload", "kinematic2d", "--n-sd", str(2**17), "--steps", "6",
+              "--warmup", "2", "--reps", "2", "--no-cpu-baseline", "--roofline-steps", "2"]
     lines = {}
     for gpus in (1, 2):
         done = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus",
