@@ -20,6 +20,8 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "sdm_hip.h")
+# the condensation path has a header of its own (implemented by libsdm_hip.so, not by the oracle)
+CONDENSATION_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "sdm_condensation.h")
 # SDM_HIP_LIB: another build of the same library (tuning variants); still no fallback
 HIP_LIB_PATH = os.environ.get("SDM_HIP_LIB") or os.path.join(_HERE, "libsdm_hip.so")
 
@@ -202,18 +204,20 @@ def declared_symbols():
 
 
 class Library:
-    """a shared library implementing include/sdm_hip.h, with checked, converting callables"""
+    """a shared library implementing a header (include/sdm_hip.h unless `header` names another),
+    with checked, converting callables"""
 
-    def __init__(self, path, what):
+    def __init__(self, path, what, header=HEADER_PATH):
         if not os.path.exists(path):
             raise ImportError(f"{path} is missing ({what}); build it with "
                               f"`python -c 'import __graft_entry__ as g; g.build()'`")
         self.path = path
         self.cdll = ctypes.CDLL(path)
-        self.signatures = parse_header()
+        self.signatures = parse_header(header)
         missing = [name for name in self.signatures if not hasattr(self.cdll, name)]
         if missing:
-            raise ImportError(f"{path} lacks symbols declared in sdm_hip.h: {missing}")
+            raise ImportError(f"{path} lacks symbols declared in {os.path.basename(header)}: "
+                              f"{missing}")
         for name, (ret, _) in self.signatures.items():
             getattr(self.cdll, name).restype = ctypes.c_char_p if ret == "str" else c_int
 
@@ -240,6 +244,7 @@ class Library:
 
 
 _hip_library = None
+_condensation_library = None
 
 
 def hip_library():
@@ -248,6 +253,15 @@ def hip_library():
     if _hip_library is None:
         _hip_library = Library(HIP_LIB_PATH, "the HIP kernels of pysdm_amd")
     return _hip_library
+
+
+def condensation_library():
+    """libsdm_hip.so bound to include/sdm_condensation.h (same file, same contexts)"""
+    global _condensation_library  # pylint: disable=global-statement
+    if _condensation_library is None:
+        _condensation_library = Library(HIP_LIB_PATH, "the HIP kernels of pysdm_amd",
+                                        header=CONDENSATION_HEADER_PATH)
+    return _condensation_library
 
 
 def pcg64_state_inc(seed):

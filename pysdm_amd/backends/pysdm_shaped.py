@@ -17,6 +17,7 @@ import warnings
 import numpy as np
 
 from ..abi import pcg64_state_inc
+from ..condensation import check_formulae, condensation_call, constants_of
 from ..displacement import SCHEMES
 from ..formulae import Formulae
 from .storage import storage_class_for
@@ -385,6 +386,76 @@ def backend_class_for(engine_getter, name, doc=None):  # pylint: disable=too-man
                      typed(attr_data, flt), cell_id.data, idx.data, int(length), float(rank),
                      typed(x_bins, flt), int(moments.shape[0]), int(moments.shape[1]),
                      typed(x_attr, flt), typed(weighting_attribute, flt), float(weighting_rank))
+
+        # ---- condensation (condensation_methods.py; include/sdm_condensation.h) -------------------
+        def make_condensation_solver(self, timestep, n_cell, *, dt_range, adaptive, fuse,
+                                     multiplier, RH_rtol, max_iters):
+            """the solver's parameters (the whole solver runs in `sdm_condensation`); the checks
+            of make_adapt_substeps (condensation_methods.py:181-188)"""
+            check_formulae(self.formulae)
+            if not isinstance(multiplier, int):
+                raise ValueError()
+            if dt_range[0] == 0:
+                raise NotImplementedError()
+            return {"timestep": float(timestep), "n_cell": int(n_cell),
+                    "dt_range": (float(dt_range[0]), float(dt_range[1])),
+                    "adaptive": bool(adaptive), "fuse": int(fuse), "multiplier": multiplier,
+                    "RH_rtol": float(RH_rtol), "max_iters": int(max_iters)}
+
+        def condensation(self, *, solver, n_cell, cell_start_arg, water_mass, multiplicity, vdry,
+                         idx, rhod, thd, water_vapour_mixing_ratio, dv, prhod, pthd,
+                         predicted_water_vapour_mixing_ratio, kappa, f_org, rtol_x, rtol_thd,
+                         v_cr, timestep, counters, cell_order, RH_max, success, cell_id,
+                         reynolds_number, air_density, air_dynamic_viscosity):  # pylint: disable=unused-argument
+            eng = self.engine
+            cell_order = np.ascontiguousarray(np.asarray(cell_order), dtype=np.int64)
+            condensation_call(
+                eng, formulae=self.formulae, n_sd=int(water_mass.shape[0]), n_cell=n_cell,
+                cell_start=cell_start_arg.data, water_mass=water_mass.data, v_cr=v_cr.data,
+                multiplicity=multiplicity.data, vdry=vdry.data, idx=idx.data, rhod=rhod.data,
+                thd=thd.data, water_vapour_mixing_ratio=water_vapour_mixing_ratio.data, dv=dv,
+                prhod=prhod.data, pthd=pthd.data,
+                predicted_water_vapour_mixing_ratio=predicted_water_vapour_mixing_ratio.data,
+                kappa=kappa.data, f_org=f_org.data, rtol_x=rtol_x, rtol_thd=rtol_thd,
+                timestep=timestep, counters={k: v.data for k, v in counters.items()},
+                cell_order=eng.upload(cell_order), RH_max=RH_max.data, success=success.data,
+                reynolds_number=reynolds_number.data, air_density=air_density.data,
+                air_dynamic_viscosity=air_dynamic_viscosity.data,
+                dt_range=(solver["dt_range"][0], min(solver["dt_range"][1], float(timestep))),
+                adaptive=solver["adaptive"], fuse=solver["fuse"],
+                multiplier=solver["multiplier"], RH_rtol=solver["RH_rtol"],
+                max_iters=solver["max_iters"])
+
+        # ---- ambient thermodynamics (physics_methods.py) ----------------------------------------
+        def temperature_pressure_rh(self, *, rhod, thd, water_vapour_mixing_ratio, T, p, RH):
+            self.engine.call_condensation(
+                "sdm_temperature_pressure_rh", rhod.data, thd.data,
+                water_vapour_mixing_ratio.data, T.data, p.data, RH.data, int(T.shape[0]),
+                constants_of(self.formulae))
+
+        def air_density(self, *, output, rhod, water_vapour_mixing_ratio):
+            self.engine.call_condensation("sdm_air_density", output.data, rhod.data,
+                                          water_vapour_mixing_ratio.data, int(output.shape[0]))
+
+        def air_dynamic_viscosity(self, *, output, temperature):
+            self.engine.call_condensation("sdm_air_dynamic_viscosity", output.data,
+                                          temperature.data, int(output.shape[0]),
+                                          constants_of(self.formulae))
+
+        def critical_volume(self, *, v_cr, kappa, f_org, v_dry, v_wet, T, cell):
+            self.engine.call_condensation(
+                "sdm_critical_volume", v_cr.data, kappa.data, f_org.data, v_dry.data, v_wet.data,
+                T.data, cell.data, int(v_cr.shape[0]), constants_of(self.formulae))
+
+        def reynolds_number(self, *, output, cell_id, dynamic_viscosity, density, radius,
+                            velocity_wrt_air):
+            self.engine.call_condensation(
+                "sdm_reynolds_number", output.data, cell_id.data, dynamic_viscosity.data,
+                density.data, radius.data, velocity_wrt_air.data, int(output.shape[0]))
+
+        def explicit_euler(self, y, dt, dy_dt):
+            self.engine.call_condensation("sdm_explicit_euler", y.data, int(y.shape[0]),
+                                          float(dt), float(dy_dt))
 
     Backend.Storage = Storage
     Backend.Random = Random

@@ -1,0 +1,210 @@
+"""Condensation / evaporation on the library (include/sdm_condensation.h).
+
+`CondensationSetup` holds the parameters of PySDM's `Condensation` dynamic and of its solver
+(PySDM/dynamics/condensation.py:13-81: rtol_x, rtol_thd, dt_cond_range, adaptive, schedule,
+substeps, max_iters; fuse = 32, multiplier = 2, RH_rtol = 1e-7 as it registers them);
+`CondensationRunner` steps a `Population` with per-cell ambient columns (`AmbientColumns`) through
+`sdm_condensation`, one call per time step, the whole adaptive sub-stepping inside the library.
+
+Only PySDM's default formulae are supported (`check_formulae`); any other choice of an option
+this path depends on raises NotImplementedError naming the option.
+"""
+from dataclasses import dataclass
+from typing import Tuple
+
+import numpy as np
+
+from .engine import FLOAT, INT
+from .formulae import CONDENSATION_DEFAULTS
+
+# the order of include/sdm_condensation.h SDM_COND_K_*
+CONSTANT_NAMES = (
+    "rho_w", "Rv", "Rd", "c_pd", "c_pv", "c_pw", "l_tri", "T_tri", "T0", "p1000", "eps", "sgm_w",
+    "D0", "K0", "MAC", "HAC", "PI", "PI_4_3", "Rd_over_c_pd", "ONE_THIRD", "THREE",
+    *(f"FWC_C{i}" for i in range(9)),
+    *(f"ZOGRAFOS_1987_COEFF_T{i}" for i in (3, 2, 1, 0)),
+)
+REQUIRED_OPTIONS = {**CONDENSATION_DEFAULTS, "particle_shape_and_density": "LiquidSpheres"}
+COUNTERS = ("n_substeps", "n_activating", "n_deactivating", "n_ripening")
+
+
+def _option_name(value):
+    if isinstance(value, str):
+        return value
+    return getattr(value, "__name__", type(value).__name__)
+
+
+def check_formulae(formulae):
+    """refuses every formulae choice other than PySDM's default on the condensation path"""
+    for option, default in REQUIRED_OPTIONS.items():
+        value = getattr(formulae, option, None)
+        if value is None:
+            raise NotImplementedError(f"condensation: formulae lack `{option}`")
+        name = _option_name(value)
+        if name != default:
+            raise NotImplementedError(
+                f"condensation on this backend supports {option}={default!r} only, "
+                f"not {name!r}")
+
+
+def constants_of(formulae):
+    """`formulae.constants` as the `consts` array of include/sdm_condensation.h"""
+    check_formulae(formulae)
+    k = formulae.constants
+    return [float(getattr(k, name)) for name in CONSTANT_NAMES]
+
+
+@dataclass(frozen=True)
+class CondensationSetup:  # pylint: disable=too-many-instance-attributes
+    """PySDM's `Condensation(...)` keywords and the solver parameters it registers"""
+
+    rtol_x: float = 1e-6
+    rtol_thd: float = 1e-6
+    dt_cond_range: Tuple[float, float] = (1e-4, 1.0)
+    adaptive: bool = True
+    substeps: int = 1
+    schedule: str = "dynamic"
+    max_iters: int = 16
+    fuse: int = 32
+    multiplier: int = 2
+    RH_rtol: float = 1e-7
+
+    def __post_init__(self):
+        if self.adaptive and self.substeps != 1:
+            raise ValueError("if specifying substeps count manually, adaptivity must be disabled")
+        if self.schedule not in ("dynamic", "static"):
+            raise NotImplementedError(self.schedule)
+        if not isinstance(self.multiplier, int):
+            raise ValueError("multiplier must be an int")
+        if self.dt_cond_range[0] == 0:
+            raise NotImplementedError("dt_cond_range[0] == 0")
+
+
+def condensation_call(engine, *, formulae, n_sd, n_cell, cell_start, water_mass, v_cr,
+                      multiplicity, vdry, idx, rhod, thd, water_vapour_mixing_ratio, dv, prhod,
+                      pthd, predicted_water_vapour_mixing_ratio, kappa, f_org, rtol_x, rtol_thd,
+                      timestep, counters, cell_order, RH_max, success, reynolds_number,
+                      air_density, air_dynamic_viscosity, dt_range, adaptive, fuse, multiplier,
+                      RH_rtol, max_iters):
+    """one `sdm_condensation` call with raw engine arrays (the argument order of the header)"""
+    engine.call_condensation(
+        "sdm_condensation", int(n_sd), int(n_cell), cell_start, water_mass, v_cr, multiplicity,
+        vdry, idx, rhod, thd, water_vapour_mixing_ratio, float(dv), prhod, pthd,
+        predicted_water_vapour_mixing_ratio, kappa, f_org, float(rtol_x), float(rtol_thd),
+        float(timestep), counters["n_substeps"], counters["n_activating"],
+        counters["n_deactivating"], counters["n_ripening"], cell_order, RH_max, success,
+        reynolds_number, air_density, air_dynamic_viscosity, float(dt_range[0]),
+        float(dt_range[1]), int(bool(adaptive)), int(fuse), int(multiplier), float(RH_rtol),
+        int(max_iters), constants_of(formulae))
+
+
+class AmbientColumns:  # pylint: disable=too-few-public-methods,too-many-instance-attributes
+    """per-cell ambient state of a Population: rhod, thd, qv (water vapour mixing ratio), their
+    predicted values, air density and air dynamic viscosity (engine arrays of n_cell)"""
+
+    def __init__(self, engine, formulae, *, rhod, thd, qv, prhod=None, pthd=None, pqv=None):
+        up = engine.upload
+        as_f = lambda v: np.asarray(v, dtype=float)  # noqa: E731
+        self.engine, self.formulae = engine, formulae
+        self.rhod, self.thd, self.qv = up(as_f(rhod)), up(as_f(thd)), up(as_f(qv))
+        self.prhod = up(as_f(rhod if prhod is None else prhod))
+        self.pthd = up(as_f(thd if pthd is None else pthd))
+        self.pqv = up(as_f(qv if pqv is None else pqv))
+        n_cell = int(np.asarray(rhod).shape[0])
+        self.T, self.p, self.RH = (engine.empty(n_cell, FLOAT) for _ in range(3))
+        self.air_density = engine.empty(n_cell, FLOAT)
+        self.air_dynamic_viscosity = engine.empty(n_cell, FLOAT)
+        self.update()
+
+    def update(self):
+        """T, p, RH, air density and viscosity from rhod / thd / qv (Moist.sync,
+        environments/impl/moist.py:60-100)"""
+        eng, n = self.engine, self.engine.size(self.rhod)
+        consts = constants_of(self.formulae)
+        eng.call_condensation("sdm_temperature_pressure_rh", self.rhod, self.thd, self.qv, self.T,
+                              self.p, self.RH, n, consts)
+        eng.call_condensation("sdm_air_density", self.air_density, self.rhod, self.qv, n)
+        eng.call_condensation("sdm_air_dynamic_viscosity", self.air_dynamic_viscosity, self.T, n,
+                              consts)
+
+    def accept_predictions(self):
+        """the predicted thd / qv (what condensation wrote) become the state"""
+        self.engine.assign(self.thd, self.pthd)
+        self.engine.assign(self.qv, self.pqv)
+        self.engine.assign(self.rhod, self.prhod)
+        self.update()
+
+
+class CondensationRunner:  # pylint: disable=too-many-instance-attributes
+    """PySDM's `Condensation` dynamic over a Population: per-droplet `dry volume`, `kappa`,
+    `dry volume organic fraction`, `critical volume` (and `Reynolds number`, an argument only
+    while ventilation is Neglect) next to the Population's water masses, per-cell counters"""
+
+    def __init__(self, population, ambient, setup, *, timestep, dv, dry_volume, kappa,
+                 f_org=None, formulae=None):
+        self.population, self.ambient, self.setup = population, ambient, setup
+        self.formulae = formulae or ambient.formulae
+        check_formulae(self.formulae)
+        eng = self.engine = population.engine
+        n_sd, n_cell = population.n_sd, population.n_cell
+        self.timestep, self.dv = float(timestep), float(dv)
+        self.dt_range = (setup.dt_cond_range[0], min(setup.dt_cond_range[1], self.timestep))
+        self.dry_volume = eng.upload(np.asarray(dry_volume, dtype=float))
+        self.kappa = eng.upload(np.asarray(kappa, dtype=float))
+        self.f_org = eng.upload(np.zeros(n_sd) if f_org is None
+                                else np.asarray(f_org, dtype=float))
+        self.critical_volume = eng.empty(n_sd, FLOAT)
+        self.reynolds_number = eng.zeros(n_sd, FLOAT)
+        start = setup.substeps if not setup.adaptive else -1
+        self.counters = {k: eng.full(n_cell, INT, start if k == "n_substeps" else -1)
+                         for k in COUNTERS}
+        self.RH_max = eng.full(n_cell, FLOAT, np.nan)
+        self.success = eng.zeros(n_cell, np.uint8)
+        self.cell_order = np.arange(n_cell, dtype=np.int64)
+
+    def update_critical_volume(self):
+        """attributes/physics/critical_volume.py: v_cr at the temperature of each droplet's cell"""
+        pop = self.population
+        self.engine.call_condensation(
+            "sdm_critical_volume", self.critical_volume, self.kappa, self.f_org, self.dry_volume,
+            pop.volume(), self.ambient.T, pop.cell_id, pop.n_sd, constants_of(self.formulae))
+
+    def step(self):
+        """one `Condensation()` call: predicted thd / qv and water masses updated, then the
+        predictions accepted and T, p, RH refreshed (particulator.update_TpRH)"""
+        pop, amb, eng, setup = self.population, self.ambient, self.engine, self.setup
+        pop.refresh_bookkeeping()
+        cell_start = pop.sorted_cell_start()
+        if setup.schedule == "dynamic":  # dynamics/condensation.py:84-85
+            self.cell_order = np.argsort(eng.download(self.counters["n_substeps"]))
+        self.update_critical_volume()
+        condensation_call(
+            eng, formulae=self.formulae, n_sd=pop.n_sd, n_cell=pop.n_cell, cell_start=cell_start,
+            water_mass=pop.mass, v_cr=self.critical_volume, multiplicity=pop.multiplicity,
+            vdry=self.dry_volume, idx=pop.perm, rhod=amb.rhod, thd=amb.thd,
+            water_vapour_mixing_ratio=amb.qv, dv=self.dv, prhod=amb.prhod, pthd=amb.pthd,
+            predicted_water_vapour_mixing_ratio=amb.pqv, kappa=self.kappa, f_org=self.f_org,
+            rtol_x=setup.rtol_x, rtol_thd=setup.rtol_thd, timestep=self.timestep,
+            counters=self.counters, cell_order=eng.upload(self.cell_order.astype(np.int64)),
+            RH_max=self.RH_max, success=self.success, reynolds_number=self.reynolds_number,
+            air_density=amb.air_density, air_dynamic_viscosity=amb.air_dynamic_viscosity,
+            dt_range=self.dt_range, adaptive=setup.adaptive, fuse=setup.fuse,
+            multiplier=setup.multiplier, RH_rtol=setup.RH_rtol, max_iters=setup.max_iters)
+        pop.touch_state()
+        if not eng.download(self.success).all():
+            raise RuntimeError("Condensation failed")
+        amb.accept_predictions()
+        if setup.adaptive:  # dynamics/condensation.py:104-115
+            n = eng.download(self.counters["n_substeps"])
+            n = np.maximum(n, int(self.timestep / setup.dt_cond_range[1]))
+            n = np.minimum(n, int(self.timestep / setup.dt_cond_range[0]))
+            eng.assign(self.counters["n_substeps"], eng.upload(n.astype(np.int64)))
+
+    def snapshot(self):
+        """host copies: water masses, ambient state and the per-cell counters"""
+        down, amb = self.engine.download, self.ambient
+        out = {"water_mass": down(self.population.mass), "thd": down(amb.thd),
+               "qv": down(amb.qv), "rhod": down(amb.rhod), "RH_max": down(self.RH_max),
+               "success": down(self.success)}
+        out.update({k: down(v) for k, v in self.counters.items()})
+        return out

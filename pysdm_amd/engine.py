@@ -21,6 +21,8 @@ class Engine:
     name = "abstract"
     library = None
     handle = None
+    # the implementation of include/sdm_condensation.h that goes with `library` (same contexts)
+    condensation_library = None
 
     # ---- arrays -----------------------------------------------------------------------------
     def empty(self, shape, dtype):
@@ -61,6 +63,13 @@ class Engine:
         self._before_call()
         self.library.invoke(symbol, self.handle, args)
 
+    def call_condensation(self, symbol, *args):
+        """a symbol of include/sdm_condensation.h"""
+        if self.condensation_library is None:
+            raise NotImplementedError(f"engine `{self.name}` has no condensation library")
+        self._before_call()
+        self.condensation_library.invoke(symbol, self.handle, args)
+
     def _before_call(self):
         pass
 
@@ -85,6 +94,7 @@ class HipEngine(Engine):
 
         self.torch = torch
         self.library = abi.hip_library()
+        self.condensation_library = abi.condensation_library()
         self.handle = abi.c_ptr()
         self.library.check(self.library.cdll.sdm_ctx_create(ctypes.byref(self.handle),
                                                             abi.c_int(device_index)))

@@ -12,6 +12,22 @@ import numpy as np
 from .physics import constants as _const
 
 
+# PySDM/formulae.py:27-67 defaults of the options the condensation path depends on
+CONDENSATION_DEFAULTS = {
+    "diffusion_coordinate": "WaterMassLogarithm",
+    "saturation_vapour_pressure": "FlatauWalkoCotton",
+    "latent_heat_vapourisation": "Kirchhoff",
+    "hygroscopicity": "KappaKoehlerLeadingTerms",
+    "drop_growth": "Mason1971",
+    "surface_tension": "Constant",
+    "diffusion_kinetics": "FuchsSutugin",
+    "diffusion_thermics": "Neglect",
+    "ventilation": "Neglect",
+    "state_variable_triplet": "LibcloudphPlusPlus",
+    "air_dynamic_viscosity": "ZografosEtAl1987",
+}
+
+
 class _Trivia:  # PySDM/physics/trivia.py:19-28
     @staticmethod
     def volume(radius):
@@ -68,9 +84,18 @@ class Formulae:  # pylint: disable=too-few-public-methods,too-many-arguments
         terminal_velocity="GunnKinzer1949",
         handle_all_breakups=False,
         particle_advection="ImplicitInSpace",
+        **condensation_options,
     ):
         if particle_shape_and_density != "LiquidSpheres":
             raise NotImplementedError(particle_shape_and_density)
+        # the condensation path supports PySDM's defaults only (pysdm_amd/condensation.py)
+        for option, value in condensation_options.items():
+            if option not in CONDENSATION_DEFAULTS:
+                raise TypeError(f"Formulae got an unexpected keyword argument '{option}'")
+            if value != CONDENSATION_DEFAULTS[option]:
+                raise NotImplementedError(f"{option}={value!r}")
+        for option, value in CONDENSATION_DEFAULTS.items():
+            setattr(self, option, SimpleNamespace(__name__=value))
         if terminal_velocity not in ("GunnKinzer1949", "RogersYau", "PowerSeries"):
             raise NotImplementedError(terminal_velocity)
         values = {

@@ -58,6 +58,39 @@ ROGERS_YAU_TERM_VEL_LARGE_K = 2.01e3 * si.cm**0.5 / si.s
 ROGERS_YAU_TERM_VEL_SMALL_R_LIMIT = 35 * si.um
 ROGERS_YAU_TERM_VEL_MEDIUM_R_LIMIT = 600 * si.um
 
+# condensation path (pysdm_amd/condensation.py): the values PySDM/physics/constants_defaults.py
+# computes (Rv = R_str / Mv, Rd = R_str / Md, eps = Mv / Md, l_tri, Rd_over_c_pd = Rd / c_pd, the
+# Flatau-Walko-Cotton coefficients in Pa, ...), written as the doubles it arrives at
+Rv = 461.523055858115
+Rd = 287.0421396862956
+c_pd = 1005.0
+c_pv = 1850.0
+c_pw = 4218.0
+l_tri = 2500711.849262262
+T_tri = 273.16
+T0 = 273.15
+p1000 = 100000.0
+eps = 0.6219453958862249
+D0 = 2.26e-05
+K0 = 0.024
+MAC = 1.0
+HAC = 1.0
+Rd_over_c_pd = 0.28561406933959765
+THREE = 3
+FWC_C0 = 611.583699
+FWC_C1 = 44.460689599999995
+FWC_C2 = 1.43177157
+FWC_C3 = 0.026422432099999997
+FWC_C4 = 0.000299291081
+FWC_C5 = 2.03154182e-06
+FWC_C6 = 7.02620698e-09
+FWC_C7 = 3.7953431e-12
+FWC_C8 = -3.2158239300000003e-14
+ZOGRAFOS_1987_COEFF_T3 = 2.5914e-15
+ZOGRAFOS_1987_COEFF_T2 = -1.4346e-11
+ZOGRAFOS_1987_COEFF_T1 = 5.0523e-08
+ZOGRAFOS_1987_COEFF_T0 = 4.113e-06
+
 
 def namespace(overrides=None):
     """the numeric constants of this module as one namespace, optionally with overrides"""
