@@ -808,6 +808,24 @@ __global__ void __launch_bounds__(SDM_BLOCK) k_pair_all(sdm_step_cfg cfg, FusedA
 // super-droplet dies in it, the next build redoes it after the compaction (k_bin_build2).  Saves
 // that sub-step a 13-us kernel with its boundary (coalescence only: the pair lists of the
 // breakup route are sized for SDM_BLOCK-thread workgroups).
+//
+// The sort only hides behind pair work that is resident on the same CU.  A workgroup of
+// BIN_THREADS = 1024 is 4 waves per SIMD, so two of them on a CU need a register budget of 8
+// waves per SIMD; left alone the compiler takes 106 SGPRs (7 waves), the runtime keeps ONE
+// workgroup per CU, and the sort workgroups - first in the grid - run before the pair work instead
+// of beside it: 10 of the kernel's 51 us at 2^20 (profiles/README.md, round 5).
+// PAIR_SORT_BUDGET asks for the 8 (the scalars that no longer fit go to VGPR lanes, no scratch):
+// every CU then starts with one sort and one pair workgroup, and the second pair workgroup takes
+// the sort's place.  The parameterized kernel cannot have the budget without scratch and stays at
+// one workgroup per CU.
+// -DPAIR_SORT_ONE_PER_CU (tuning builds): no request, the compiler's own budget, for A/B runs.
+#ifdef PAIR_SORT_ONE_PER_CU
+#define PAIR_SORT_BUDGET(K)
+#else
+#define PAIR_SORT_BUDGET(K) \
+  __attribute__((amdgpu_waves_per_eu((K) == SDM_KERNEL_PARAMETERIZED ? 4 : 8, 8)))
+#endif
+
 struct SortAhead {
   int2 *events;
   int32_t *toff, *jarr, *loc;
@@ -825,14 +843,40 @@ __device__ __forceinline__ double draw_at(u128 s_base, u128 inc, const u128 *__r
   return pcg_output(state);
 }
 
+// -DPAIR_PROFILE (tuning builds only): every workgroup of k_pair_all_sort leaves {entry, exit}
+// in wall_clock64 ticks (100 MHz), its role (0 sort, 1 pair), and where it ran (HW_ID and XCC_ID
+// registers, read only); sdm_debug_pair_profile reads the last launch back
+// (profiles/tools/pair_profile.py)
+#ifdef PAIR_PROFILE
+#define PAIR_PROF_CAP 8192
+__device__ long long pair_prof[PAIR_PROF_CAP * 4];
+#define PAIR_PROF_ENTRY() const long long prof_t0 = wall_clock64()
+#define PAIR_PROF_EXIT(role) do { \
+    __syncthreads(); \
+    if (threadIdx.x == 0 && blockIdx.x < PAIR_PROF_CAP) { \
+      long long *o = pair_prof + (size_t)blockIdx.x * 4; \
+      o[0] = prof_t0; \
+      o[1] = wall_clock64(); \
+      o[2] = (role); \
+      o[3] = ((long long)(unsigned)__builtin_amdgcn_s_getreg(20 | (31 << 11)) << 32) | \
+             (long long)(unsigned)__builtin_amdgcn_s_getreg(4 | (31 << 11)); \
+    } \
+  } while (0)
+#else
+#define PAIR_PROF_ENTRY()
+#define PAIR_PROF_EXIT(role)
+#endif
+
 template <int KERNEL>
-__global__ void __launch_bounds__(BIN_THREADS)
+__global__ void __launch_bounds__(BIN_THREADS) PAIR_SORT_BUDGET(KERNEL)
 k_pair_all_sort(sdm_step_cfg cfg, FusedArgs A, SortAhead X) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
+  PAIR_PROF_ENTRY();
   if ((int)blockIdx.x < X.n_tiles) {
     const int64_t length = *X.p_length;
     bin_sort_body<true>(smem, X.events, X.toff, X.jarr, X.loc, X.n_bins, nullptr, nullptr, 1,
                         length, length, X.s_off, A.rng_inc, A.rng_tab, nullptr, A.rng_aff);
+    PAIR_PROF_EXIT(0);
     return;
   }
   const int64_t W = A.ctl[CTL_WORK];
@@ -846,7 +890,31 @@ k_pair_all_sort(sdm_step_cfg cfg, FusedArgs A, SortAhead X) {
   if (p != 0) p /= (double)cfg.substeps;  // collision.py:279
   pair_update_body<false>(cfg, A, d, d < W / 2, p, u, 0.0, true, R.off, R.j, R.k, 2 * d + R.off,
                           true);
+  PAIR_PROF_EXIT(1);
 }
+
+#ifdef PAIR_PROFILE
+static long long pair_prof_launch[3];  // the last launch: {grid, dynamic LDS bytes, n_tiles}
+extern "C" int sdm_debug_pair_launch(long long *out) {
+  for (int k = 0; k < 3; ++k) out[k] = pair_prof_launch[k];
+  return 0;
+}
+// out: 4 words per workgroup of the last launch (at most PAIR_PROF_CAP workgroups)
+extern "C" int sdm_debug_pair_profile(long long *out, int n_workgroups) {
+  if (n_workgroups < 0 || n_workgroups > PAIR_PROF_CAP) return -1;
+  return hipMemcpyFromSymbol(out, HIP_SYMBOL(pair_prof), sizeof(long long) * 4 * n_workgroups) ==
+                 hipSuccess ? 0 : -2;
+}
+// workgroups of k_pair_all_sort<Golovin>, as last launched, that the runtime keeps on one CU
+extern "C" int sdm_debug_pair_occupancy(void) {
+  int n = -1;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_pair_all_sort<SDM_KERNEL_GOLOVIN>,
+                                                   BIN_THREADS, (size_t)pair_prof_launch[1]) !=
+      hipSuccess)
+    return -2;
+  return n;
+}
+#endif
 
 // ---- adaptive: probabilities first (per-cell min of the optimal dt is a global dependency) ---
 template <int KERNEL, bool BREAKUP>
@@ -3210,6 +3278,10 @@ static int collision_step(sdm_ctx *ctx, const sdm_step_cfg *cfg, sdm_step_state 
         X.p_length = st->cell_start + C;
         X.s_off = sdm_pcg_advance_host(rng_state, rng_inc, off);  // (off: the next draw's start)
         const dim3 grid((unsigned)(B.n_tiles + grid_for((N + 1) / 2, BIN_THREADS)));
+#ifdef PAIR_PROFILE
+        pair_prof_launch[0] = grid.x; pair_prof_launch[1] = (long long)B.lds_bytes;
+        pair_prof_launch[2] = B.n_tiles;
+#endif
         const dim3 big(BIN_THREADS);
 #define PAIR_SORT(K) hipLaunchKernelGGL((k_pair_all_sort<K>), grid, big, B.lds_bytes, s, *cfg, A, X)
         switch (cfg->kernel) {

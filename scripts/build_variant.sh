@@ -2,7 +2,8 @@
 # A/B measurement builds of the library: scripts/build_variant.sh NAME "-DFLAG ..." writes
 # build_variants/libsdm_NAME.so (git-ignored; travels to the GPU box); use with SDM_HIP_LIB=...
 # ONLY=index: the flags go to that translation unit alone (-DBIN_PROFILE: its device symbol
-# cannot be shared with fused.hip, which uses the same tile sort).  A failed compile fails the build.
+# cannot be shared with fused.hip, which uses the same tile sort; ONLY=fused for -DPAIR_PROFILE and
+# -DPAIR_SORT_ONE_PER_CU, which are k_pair_all_sort's).  A failed compile fails the build.
 set -euo pipefail
 name=$1; shift
 root=$(cd "$(dirname "$0")/.." && pwd)
