@@ -827,7 +827,7 @@ __global__ void __launch_bounds__(SDM_BLOCK) k_pair_all(sdm_step_cfg cfg, FusedA
 #endif
 
 struct SortAhead {
-  int2 *events;
+  uint32_t *events;
   int32_t *toff, *jarr, *loc;
   int n_bins, n_tiles;
   const int64_t *p_length;

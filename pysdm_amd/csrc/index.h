@@ -43,19 +43,21 @@ struct SortPrologue {
 // the re-sort it has to do itself when a super-droplet died in between
 struct BuildPrologue {
   SortPrologue compact;  // compact.fctl == NULL: none
-  // SDM_REC_CHAIN: the overflow links of the hit lists (scratch of the build); per event its place
-  // in the sorted array (from the tile sort); the S words, by that place
+  // SDM_REC_CHAIN: the overflow links of the hit lists (scratch of the build); per position the
+  // place of its own event in the sorted array, -1: none (from the tile sort); the S words, by
+  // that place
   int32_t *chain_links, *loc;
   uint32_t *ssucc;
-  int2 *events;
-  int32_t *toff, *jarr;
+  uint32_t *events;      // packed (shuffle_build.h: ev_pack)
+  int32_t *toff, *jarr;  // (jarr: NULL with SDM_REC_CHAIN - `loc` says it all)
   u128 s_off, inc;
   const u128 *tab, *aff;
 };
 // the buffers of a build, for a tile sort done elsewhere (same scratch, same size)
 struct SortBuffers {
-  int2 *events;
-  int32_t *toff, *jarr, *loc;  // (loc: NULL unless the build makes successor words)
+  uint32_t *events;
+  // (loc: NULL unless the build makes successor words; jarr: NULL where it does)
+  int32_t *toff, *jarr, *loc;
   int n_bins, n_tiles;
   size_t lds_bytes;
 };

@@ -245,7 +245,7 @@ extern "C" int sdm_debug_bin_profile(long long *out) {
 #endif
 
 template <bool RNG, int TILE>
-__global__ void k_bin_sort(int2 *events, int32_t *toff, int32_t *jarr, int32_t *loc, int n_bins,
+__global__ void k_bin_sort(uint32_t *events, int32_t *toff, int32_t *jarr, int32_t *loc, int n_bins,
                            const double *u01, const int64_t *cell_start, int64_t n_cell,
                            const int64_t *p_length, int64_t length_arg, u128 s_off, u128 inc,
                            const u128 *tab, const uint64_t *dev_off, const u128 *aff);
@@ -253,7 +253,7 @@ __global__ void k_bin_sort(int2 *events, int32_t *toff, int32_t *jarr, int32_t *
 // (BuildPrologue: index.h; the kernel is defined after the compaction code it may have to run)
 template <int FMT>
 __global__ void k_bin_build2(void *rec_out, int32_t *ovf_head, int32_t *ovf_next,
-                             const int2 *events, const int32_t *toff, const int32_t *jarr,
+                             const uint32_t *events, const int32_t *toff, const int32_t *jarr,
                              int n_bins, int n_tiles, int ev_tile, const int64_t *idx0,
                              const int64_t *p_length, int64_t length_arg, BuildPrologue P);
 
@@ -325,20 +325,29 @@ static int shuffle_binned_async(sdm_ctx *ctx, char *scratch, int64_t *out, const
   int32_t *ovf_head = cv.take<int32_t>(length_bound);
   int32_t *ovf_next = cv.take<int32_t>(length_bound);
   int32_t *jarr = cv.take<int32_t>(length_bound);
-  int2 *events = cv.take<int2>((size_t)nt * tile);
+  // (the carve keeps the sizes of 8-byte events; the packed ones use the first half)
+  uint32_t *events = (uint32_t *)cv.take<int2>((size_t)nt * tile);
   int32_t *toff = cv.take<int32_t>((size_t)(nb + 1) * nt);
   // SDM_REC_CHAIN: the record buffer's 16 B per position hold four int32 arrays of nt * EV_TILE
-  // words instead - first | overflow links | loc (event -> place in `events`) | ssucc (by place)
+  // words instead - first | overflow links | loc (position -> place of its event in `events`, -1:
+  // it has none) | ssucc (by place).  `jarr` is not used then: its sign is loc's
   const size_t padded = (size_t)nt * tile;
   int32_t *chain = (int32_t *)rec;
   int32_t *loc = fmt == SDM_REC_CHAIN ? chain + 2 * padded : nullptr;
+  if (fmt == SDM_REC_CHAIN) jarr = nullptr;
+  if (presorted) {
+    // the pair kernel that sorted ahead wrote either `loc` or `jarr`: it must have chosen as this
+    // build does (sdm_shuffle_sort_buffers states the same condition from the length alone)
+    SortBuffers ahead;
+    sdm_shuffle_sort_buffers(ctx, scratch, length_bound, &ahead);
+    ARG_TRY((ahead.loc != nullptr) == (fmt == SDM_REC_CHAIN) && ahead.loc == loc);
+  }
   const dim3 block(BIN_THREADS);
-  const size_t lds_sort = sizeof(int32_t) * (size_t)((nb + 1) + ((nb + 1) & ~1) + 2) +
-                          sizeof(int2) * tile;
+  const size_t lds_sort = bin_sort_lds_bytes(nb, tile);
   // (64 KB with three inline slots - two workgroups per CU - 80 KB with four; the prologue of a
   // presorted build sorts in the same memory)
-  // (SDM_REC_CHAIN: + own target, id and place of every position of the bin)
-  size_t lds_build = sizeof(int32_t) * (size_t)((slots + 1 + (fmt == SDM_REC_CHAIN ? 3 : 0)) * BIN_POS);
+  // (SDM_REC_CHAIN: + id and place of its own event of every position of the bin)
+  size_t lds_build = sizeof(int32_t) * (size_t)((slots + 1 + (fmt == SDM_REC_CHAIN ? 2 : 0)) * BIN_POS);
   if (presorted && lds_sort > lds_build) lds_build = lds_sort;
   // gfx950 has 160 KiB of LDS per CU; > 64 KiB dynamic needs opting in (per kernel and device)
   if (lds_sort > 65536) {
@@ -444,12 +453,12 @@ void sdm_shuffle_sort_buffers(sdm_ctx *ctx, char *scratch, int64_t length_bound,
   out->loc = chain_enabled(ctx) && length_bound <= CHAIN_MAX && nb * 16 <= EV_TILE
                  ? chain + 2 * (size_t)nt * EV_TILE : nullptr;
   out->jarr = cv.take<int32_t>(length_bound);
-  out->events = cv.take<int2>((size_t)nt * EV_TILE);
+  if (out->loc) out->jarr = nullptr;
+  out->events = (uint32_t *)cv.take<int2>((size_t)nt * EV_TILE);
   out->toff = cv.take<int32_t>((size_t)(nb + 1) * nt);
   out->n_bins = nb;
   out->n_tiles = nt;
-  out->lds_bytes = sizeof(int32_t) * (size_t)((nb + 1) + ((nb + 1) & ~1) + 2) +
-                   sizeof(int2) * EV_TILE;
+  out->lds_bytes = bin_sort_lds_bytes(nb, EV_TILE);
 }
 
 size_t sdm_shuffle_scratch(int64_t n) {
@@ -893,7 +902,7 @@ k_compact_persistent(const int64_t *__restrict__ multiplicity, int64_t *__restri
 // k_bin_sort (declared above): the tile sort of the shuffle build
 template <bool RNG, int TILE>
 __global__ void __launch_bounds__(BIN_THREADS)
-k_bin_sort(int2 *__restrict__ events, int32_t *__restrict__ toff, int32_t *__restrict__ jarr,
+k_bin_sort(uint32_t *__restrict__ events, int32_t *__restrict__ toff, int32_t *__restrict__ jarr,
            int32_t *__restrict__ loc, int n_bins, const double *__restrict__ u01,
            const int64_t *__restrict__ cell_start,
            int64_t n_cell, const int64_t *__restrict__ p_length, int64_t length_arg, u128 s_off,
@@ -908,7 +917,7 @@ k_bin_sort(int2 *__restrict__ events, int32_t *__restrict__ toff, int32_t *__res
 template <int FMT>
 __global__ void __launch_bounds__(BIN_THREADS)
 k_bin_build2(void *__restrict__ rec_out, int32_t *__restrict__ ovf_head,
-             int32_t *__restrict__ ovf_next, const int2 *__restrict__ events,
+             int32_t *__restrict__ ovf_next, const uint32_t *__restrict__ events,
              const int32_t *__restrict__ toff, const int32_t *__restrict__ jarr, int n_bins,
              int n_tiles, int ev_tile, const int64_t *__restrict__ idx0,
              const int64_t *__restrict__ p_length, int64_t length_arg, BuildPrologue P) {
@@ -919,8 +928,9 @@ k_bin_build2(void *__restrict__ rec_out, int32_t *__restrict__ ovf_head,
   constexpr int SLOTS = FMT == SDM_REC_CHAIN ? 5 : FMT == SDM_REC_P21 ? 4 : (FMT == SDM_REC_P24 ? 3 : 2);
   int32_t *slot = (int32_t *)smem;  // SLOTS x BIN_POS, then BIN_POS list heads
   int32_t *head = slot + SLOTS * BIN_POS;
-  // SDM_REC_CHAIN: own target / id / place in the sorted array of every position of the bin
-  int32_t *jp_l = head + BIN_POS, *id_l = jp_l + BIN_POS, *loc_l = id_l + BIN_POS;
+  // SDM_REC_CHAIN: id / place of its own event in the sorted array (-1: it has none) of every
+  // position of the bin
+  int32_t *id_l = head + BIN_POS, *loc_l = id_l + BIN_POS;
   // P.compact.fctl: the events were sorted ahead, by the pair kernel of the previous sub-step, for
   // the length that sub-step began with.  If a super-droplet died in it (rare), the compaction
   // runs here, every workgroup sorts its tile again for the new length (n_tiles == n_bins on this
@@ -970,13 +980,14 @@ k_bin_build2(void *__restrict__ rec_out, int32_t *__restrict__ ovf_head,
   constexpr int RUN_AHEAD = 8;
   // (the first RUN_AHEAD events of the thread's FIRST tile - at 2^20 positions its only one - stay
   // in registers: the S pass below needs the same events again)
-  int2 ev0[RUN_AHEAD];
+  // (packed: a word each, unpacked with the tile's and this bin's base where they are used)
+  uint32_t ev0[RUN_AHEAD];
   {
-    const int2 *run = events + (int64_t)t_first * ev_tile;
+    const uint32_t *run = events + (int64_t)t_first * ev_tile;
 #pragma unroll
     for (int k = 0; k < RUN_AHEAD; ++k) {
       const int x = a_first + sub + k * tpt;
-      ev0[k] = x < b_first ? run[x] : make_int2(-1, 0);  // (b_first = 0 beyond the last tile)
+      ev0[k] = x < b_first ? run[x] : EV_NONE;  // (b_first = 0 beyond the last tile)
     }
   }
   // what the records need from memory besides the hits, requested now, used at the end
@@ -986,7 +997,7 @@ k_bin_build2(void *__restrict__ rec_out, int32_t *__restrict__ ovf_head,
   for (int k = 0; k < PER_POS; ++k) {
     const int64_t p = base + threadIdx.x + k * BIN_THREADS;
     id_v[k] = p < length ? idx0[p] : 0;
-    j_v[k] = p < length ? jarr[p] : -1;
+    j_v[k] = (FMT != SDM_REC_CHAIN && p < length) ? jarr[p] : -1;
     loc_v[k] = (FMT == SDM_REC_CHAIN && p < length) ? P.loc[p] : -1;
   }
   BIN_MARK(9);
@@ -1012,24 +1023,25 @@ k_bin_build2(void *__restrict__ rec_out, int32_t *__restrict__ ovf_head,
       a = row[0];
       b = row[1];
     }
-    const int2 *run = events + (int64_t)t * ev_tile;  // (tile-major: the tile's own segment)
-    int2 ev[RUN_AHEAD];
+    const uint32_t *run = events + (int64_t)t * ev_tile;  // (tile-major: the tile's own segment)
+    const int32_t tile_base = t * ev_tile;
+    uint32_t ev[RUN_AHEAD];
 #pragma unroll
     for (int k = 0; k < RUN_AHEAD; ++k) {
       const int x = a + sub + k * tpt;
-      ev[k] = t == t_first ? ev0[k] : (x < b ? run[x] : make_int2(-1, 0));
+      ev[k] = t == t_first ? ev0[k] : (x < b ? run[x] : EV_NONE);
     }
 #pragma unroll
     for (int k = 0; k < RUN_AHEAD; ++k)
-      if (ev[k].x >= 0) place(ev[k]);
-    for (int x = a + sub + RUN_AHEAD * tpt; x < b; x += tpt) place(run[x]);
+      if (ev[k] != EV_NONE) place(ev_unpack(ev[k], tile_base, (int32_t)base));
+    for (int x = a + sub + RUN_AHEAD * tpt; x < b; x += tpt)
+      place(ev_unpack(run[x], tile_base, (int32_t)base));
   }
   if (FMT == SDM_REC_CHAIN) {
     // (the loads requested at the kernel's start have long arrived)
 #pragma unroll
     for (int k = 0; k < PER_POS; ++k) {
       const int q = threadIdx.x + k * BIN_THREADS;
-      jp_l[q] = j_v[k];
       id_l[q] = (int32_t)id_v[k];
       loc_l[q] = loc_v[k];
     }
@@ -1037,7 +1049,7 @@ k_bin_build2(void *__restrict__ rec_out, int32_t *__restrict__ ovf_head,
   __syncthreads();
   BIN_MARK(11);
   // SDM_REC_CHAIN (shuffle_device.h): everything that touches a position of this bin is in LDS now -
-  // its own event (jp_l >= 0: it has one) and the events that hit it (inline slots, the overflow
+  // its own event (loc_l >= 0: it has one) and the events that hit it (inline slots, the overflow
   // list this workgroup has just built).  F(q, e): what the content of position q is once all
   // events above e have been applied, as a successor word
   int32_t *links = P.chain_links;
@@ -1055,7 +1067,7 @@ k_bin_build2(void *__restrict__ rec_out, int32_t *__restrict__ ovf_head,
   auto value_after = [&](int q, int32_t e) -> uint32_t {
     const int32_t up = hit_above(q, e);
     const int32_t pi = (int32_t)base + q;
-    const int32_t own = (jp_l[q] >= 0 && pi > e) ? pi : INT32_MAX;
+    const int32_t own = (loc_l[q] >= 0 && pi > e) ? pi : INT32_MAX;
     if (up == INT32_MAX && own == INT32_MAX) return chain_word(0, id_l[q]);
     return own <= up ? chain_word(CHAIN_S, loc_l[q]) : chain_word(CHAIN_T, up);
   };
@@ -1069,18 +1081,22 @@ k_bin_build2(void *__restrict__ rec_out, int32_t *__restrict__ ovf_head,
         a = row[0];
         b = row[1];
       }
-      const int2 *run = events + (int64_t)t * ev_tile;
+      const uint32_t *run = events + (int64_t)t * ev_tile;
+      const int32_t tile_base = t * ev_tile;
       uint32_t *out = P.ssucc + (int64_t)t * ev_tile;
       int x = a + sub;
       if (t == t_first) {  // from the registers of the placing pass
 #pragma unroll
         for (int k = 0; k < RUN_AHEAD; ++k) {
-          if (ev0[k].x >= 0) out[x] = value_after(ev0[k].y - (int)base, ev0[k].x);
+          if (ev0[k] != EV_NONE) {
+            const int2 e = ev_unpack(ev0[k], tile_base, (int32_t)base);
+            out[x] = value_after(e.y - (int)base, e.x);
+          }
           x += tpt;
         }
       }
       for (; x < b; x += tpt) {
-        const int2 e = run[x];
+        const int2 e = ev_unpack(run[x], tile_base, (int32_t)base);
         out[x] = value_after(e.y - (int)base, e.x);
       }
     }
@@ -1195,7 +1211,7 @@ bool sdm_shuffle_presort_ok(sdm_ctx *ctx, int64_t length_bound, int64_t id_bound
   if (nb != nt || nb > COMPACT_MAX_GROUPS || id_bound < 0 || both > P21_MAX) return false;
   if (ctx->build_resident == 0) {
     const bool chain = chain_enabled(ctx) && nb * 16 <= EV_TILE;
-    const size_t lds_build = sizeof(int32_t) * (size_t)((chain ? 9 : 5) * BIN_POS);
+    const size_t lds_build = sizeof(int32_t) * (size_t)((chain ? 8 : 5) * BIN_POS);
     int per_cu = 0, cus = 0;
     const void *kernel = chain ? (const void *)k_bin_build2<SDM_REC_CHAIN>
                                          : (const void *)k_bin_build2<SDM_REC_P21>;

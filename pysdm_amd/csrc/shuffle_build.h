@@ -33,6 +33,50 @@ static_assert(EV_PER_THREAD * BIN_THREADS == EV_TILE && K1_THREADS * K1_PER_THRE
 
 // PackRec and the backward walk live in shuffle_device.h (shared with the fused pair kernels)
 
+// ---- packed events.  An event (index i, target j) of the tile-sorted array is read by a workgroup
+// that knows the event's tile (i's tile base) and its own bin (j's bin base), so one 32-bit word
+// holds both remainders: bits 0..15 = i - tile base, bits 16..31 = j - bin base.  EV_NONE (no
+// event) cannot be a packed one: a tile has fewer than 65535 events
+static_assert(EV_TILE <= EV_TILE_BIG && EV_TILE_BIG < 65535 && BIN_POS <= 65536, "packed events");
+#define EV_NONE 0xffffffffu
+__device__ __forceinline__ uint32_t ev_pack(int32_t i, int32_t j, int32_t tile_base,
+                                            int32_t bin_base) {
+  return (uint32_t)(i - tile_base) | ((uint32_t)(j - bin_base) << 16);
+}
+// {i, j}
+__device__ __forceinline__ int2 ev_unpack(uint32_t w, int32_t tile_base, int32_t bin_base) {
+  return make_int2(tile_base + (int32_t)(w & 0xffffu), bin_base + (int32_t)(w >> 16));
+}
+
+// ---- the tile sort's 16-byte stores (`loc`, the packed events).  When the sort rides in the pair
+// kernel its stores stream through the L2 the pair workgroups gather from, so their cache policy
+// is a compile-time choice: -DSORT_STORE=0 plain, 1 `nt`, 2 `sc1` (write-through, the line is
+// dropped from L2; only cheap at 16 bytes per lane).  Measurements: profiles/README.md, round 6.
+// Vector stores all three; `buf` + `at` words must be 16-byte aligned
+#ifndef SORT_STORE
+#define SORT_STORE 0
+#endif
+typedef int32_t sort_v4i __attribute__((ext_vector_type(4)));
+typedef uint32_t sort_v4u __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void sort_store16(void *buf, int64_t at, sort_v4i v) {
+#if SORT_STORE == 2
+  // (raw buffer store: the compiler keeps count of it like of any other store; words below 2^29)
+  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(buf, 0, 0x7fffffff, 0x00020000);
+  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(sort_v4u, v), r, (int)(at * 4), 0,
+                                         16 /* sc1 */);
+#elif SORT_STORE == 1
+  __builtin_nontemporal_store(v, (sort_v4i *)((int32_t *)buf + at));
+#else
+  *(sort_v4i *)((int32_t *)buf + at) = v;
+#endif
+}
+// dynamic LDS of the tile sort: bin starts (n_bins + 1) and counts (n_bins), rounded up to whole
+// 16 bytes, then the tile's packed events
+__host__ __device__ constexpr int bin_sort_head_words(int n_bins) { return (2 * n_bins + 2 + 3) & ~3; }
+__host__ __device__ constexpr size_t bin_sort_lds_bytes(int n_bins, int tile) {
+  return sizeof(int32_t) * ((size_t)bin_sort_head_words(n_bins) + (size_t)tile);
+}
+
 // own-event targets of BIN_PER_THREAD consecutive positions from `first` (local croupier)
 template <bool RNG, int PER>
 __device__ __forceinline__ void targets_run(int64_t first, int64_t length,
@@ -105,7 +149,10 @@ __device__ __forceinline__ int block_excl_scan(int v, int *total) {
 // ---- two launches (round 1 had four: count -> column scan -> scatter -> build; the count matrix,
 // its scan and the global scatter are gone: 32.5 -> 28.5 us of kernel time at 2^20, two launches
 // less).  K1': per event tile: own-event targets -> jarr; the tile's events ordered by target bin in LDS
-// and written back *in place* (tile-major, coalesced), with the tile's bin offsets toff[tile][0..nb].
+// and written back *in place* (tile-major, coalesced, packed: ev_pack), with the tile's bin offsets
+// toff[tile][0..nb].  `loc` != NULL (SDM_REC_CHAIN): the build wants to know of a position only
+// whether it has an event of its own and where that event stands in the sorted array, so loc[p]
+// says both (-1: none) and jarr is not written.
 // K4': one workgroup per bin gathers its runs - for every tile the events toff[t][b]..toff[t][b+1]
 // of that tile's segment, ~16 events = two 64-B sectors each, the same granularity the scatter
 // wrote at - and assembles the records as k_bin_build does.  The order of the events inside a bin
@@ -122,7 +169,7 @@ extern __device__ long long bin_prof[32];
 // `one_cell_len` >= 0: the single cell [0, length) as the caller knows it (cell_start not read)
 template <bool RNG, int TILE = EV_TILE>
 __device__ __forceinline__ void
-bin_sort_body(char *smem, int2 *__restrict__ events, int32_t *__restrict__ toff,
+bin_sort_body(char *smem, uint32_t *__restrict__ events, int32_t *__restrict__ toff,
               int32_t *__restrict__ jarr, int32_t *__restrict__ loc, int n_bins,
               const double *__restrict__ u01,
               const int64_t *__restrict__ cell_start, int64_t n_cell, int64_t length,
@@ -130,11 +177,12 @@ bin_sort_body(char *smem, int2 *__restrict__ events, int32_t *__restrict__ toff,
               const uint64_t *__restrict__ dev_off, const u128 *__restrict__ aff) {
   int32_t *lstart = (int32_t *)smem;                      // n_bins + 1
   int32_t *lcount = lstart + n_bins + 1;                  // n_bins
-  int2 *ev_buf = (int2 *)(lcount + ((n_bins + 1) & ~1));  // TILE
+  uint32_t *ev_buf = (uint32_t *)(lstart + bin_sort_head_words(n_bins));  // TILE, 16-B aligned
   __shared__ u128 s_slot;
   BIN_MARK(0);
   constexpr int PER = TILE / BIN_THREADS;  // consecutive events per thread
-  static_assert(PER * BIN_THREADS == TILE && TILE % PCG_AFF_STRIDE == 0, "tile shapes");
+  static_assert(PER * BIN_THREADS == TILE && TILE % PCG_AFF_STRIDE == 0 && PER % 4 == 0,
+                "tile shapes");
   const int64_t tile_first = (int64_t)blockIdx.x * TILE;
   int32_t *my_off = toff + (int64_t)blockIdx.x * (n_bins + 1);
   if (tile_first >= length) {
@@ -182,7 +230,7 @@ bin_sort_body(char *smem, int2 *__restrict__ events, int32_t *__restrict__ toff,
 #pragma unroll
   for (int e = 0; e < PER; ++e) {
     rank[e] = j[e] >= 0 ? atomicAdd(&lcount[j[e] >> BIN_SHIFT], 1) : 0;
-    if (first + e < length) jarr[first + e] = j[e];
+    if (!loc && first + e < length) jarr[first + e] = j[e];
   }
   __syncthreads();
   BIN_MARK(4);
@@ -203,19 +251,35 @@ bin_sort_body(char *smem, int2 *__restrict__ events, int32_t *__restrict__ toff,
   }
   __syncthreads();
   BIN_MARK(5);
+  int32_t place[PER];  // where the event stands in the sorted array, -1: the position has none
 #pragma unroll
-  for (int e = 0; e < PER; ++e)
+  for (int e = 0; e < PER; ++e) {
+    place[e] = -1;
     if (j[e] >= 0) {
       const int b = j[e] >> BIN_SHIFT;
       const int at = lstart[b] + rank[e];
-      ev_buf[at] = make_int2((int)(first + e), j[e]);
-      // (SDM_REC_CHAIN: where the event stands in the sorted array - its S word's address)
-      if (loc) loc[first + e] = (int32_t)(tile_first + at);
+      ev_buf[at] = ev_pack((int32_t)(first + e), j[e], (int32_t)tile_first, b << BIN_SHIFT);
+      place[e] = (int32_t)(tile_first + at);
     }
+  }
   __syncthreads();
   BIN_MARK(6);
   const int n_ev = lstart[n_bins];
-  for (int t = threadIdx.x; t < n_ev; t += BIN_THREADS) events[tile_first + t] = ev_buf[t];
+  // four consecutive events per store; the last one may carry up to 3 words of LDS that are no
+  // events: they stay inside the tile's own segment of `events` (n_ev <= TILE) and the build reads
+  // a segment only up to its toff
+  for (int t = threadIdx.x * 4; t < n_ev; t += BIN_THREADS * 4)
+    sort_store16(events, tile_first + t, *(const sort_v4i *)(ev_buf + t));
+  // (SDM_REC_CHAIN: the place is the address of the event's S word.)  Every position below the
+  // length is written, four positions per store.  `first` is a multiple of 4 and the last store
+  // may reach up to 3 words past the length: `loc` is padded to whole tiles (index.hip), the
+  // words land inside it and nobody reads them
+  if (loc) {
+#pragma unroll
+    for (int e = 0; e < PER; e += 4)
+      if (first + e < length)
+        sort_store16(loc, first + e, (sort_v4i){place[e], place[e + 1], place[e + 2], place[e + 3]});
+  }
   for (int b = threadIdx.x; b <= n_bins; b += BIN_THREADS) my_off[b] = lstart[b];
   BIN_MARK(7);
 }
