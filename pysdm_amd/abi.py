@@ -22,6 +22,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "sdm_hip.h")
 # the condensation path has a header of its own (implemented by libsdm_hip.so, not by the oracle)
 CONDENSATION_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "sdm_condensation.h")
+# and so has the freezing path
+FREEZING_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "sdm_freezing.h")
 # SDM_HIP_LIB: another build of the same library (tuning variants); still no fallback
 HIP_LIB_PATH = os.environ.get("SDM_HIP_LIB") or os.path.join(_HERE, "libsdm_hip.so")
 
@@ -103,6 +105,15 @@ class DispShard(ctypes.Structure):  # == sdm_disp_shard
         ("multiplicity", c_ptr), ("attributes", c_ptr), ("n_attr", ctypes.c_int32),
         ("n_moved", c_i64), ("n_left", c_i64), ("n_arrived", c_i64), ("n_words", c_i64),
         ("n_removed", c_i64),
+    ]
+
+
+class FreezingCfg(ctypes.Structure):  # == sdm_freezing_cfg (include/sdm_freezing.h)
+    _fields_ = [
+        ("singular", ctypes.c_int32), ("immersion_freezing", ctypes.c_int32),
+        ("homogeneous_freezing", ctypes.c_int32), ("thaw", ctypes.c_int32),
+        ("j_het", ctypes.c_int32), ("j_hom", ctypes.c_int32), ("rates", ctypes.c_int32),
+        ("reserved", ctypes.c_int32), ("timestep", c_f64), ("rng_state_inc", c_u64 * 4),
     ]
 
 
@@ -220,6 +231,8 @@ class Library:
                               f"{missing}")
         for name, (ret, _) in self.signatures.items():
             getattr(self.cdll, name).restype = ctypes.c_char_p if ret == "str" else c_int
+        # (declared by sdm_hip.h; the headers of the other paths use it without declaring it)
+        self.cdll.sdm_last_error.restype = ctypes.c_char_p
 
     def last_error(self):
         return self.cdll.sdm_last_error().decode()
@@ -245,6 +258,7 @@ class Library:
 
 _hip_library = None
 _condensation_library = None
+_freezing_library = None
 
 
 def hip_library():
@@ -262,6 +276,15 @@ def condensation_library():
         _condensation_library = Library(HIP_LIB_PATH, "the HIP kernels of pysdm_amd",
                                         header=CONDENSATION_HEADER_PATH)
     return _condensation_library
+
+
+def freezing_library():
+    """libsdm_hip.so bound to include/sdm_freezing.h (same file, same contexts)"""
+    global _freezing_library  # pylint: disable=global-statement
+    if _freezing_library is None:
+        _freezing_library = Library(HIP_LIB_PATH, "the HIP kernels of pysdm_amd",
+                                    header=FREEZING_HEADER_PATH)
+    return _freezing_library
 
 
 def pcg64_state_inc(seed):

@@ -17,6 +17,7 @@ import warnings
 import numpy as np
 
 from ..abi import pcg64_state_inc
+from .. import freezing as frz
 from ..condensation import check_formulae, condensation_call, constants_of
 from ..displacement import SCHEMES
 from ..formulae import Formulae
@@ -264,11 +265,24 @@ def backend_class_for(engine_getter, name, doc=None):  # pylint: disable=too-man
             call("sdm_interpolation", output.data, radius.data, int(radius.shape[0]),
                  float(factor), b.data, c.data, int(b.shape[0]))
 
+        def _mixed_phase(self):
+            return self.formulae.particle_shape_and_density.supports_mixed_phase()
+
         def volume_of_water_mass(self, volume, mass):
+            if self._mixed_phase():  # mixed_phase_spheres.py: ice (m < 0) has its own density
+                self.engine.call_freezing(
+                    "sdm_volume_of_signed_water_mass", volume.data, mass.data,
+                    int(volume.shape[0]), frz.constants_of(self.formulae))
+                return
             call("sdm_volume_of_water_mass", volume.data, mass.data, int(volume.shape[0]),
                  self.formulae.constants.rho_w)
 
         def mass_of_water_volume(self, mass, volume):
+            if self._mixed_phase():
+                self.engine.call_freezing(
+                    "sdm_signed_water_mass_of_volume", mass.data, volume.data,
+                    int(volume.shape[0]), frz.constants_of(self.formulae))
+                return
             call("sdm_mass_of_water_volume", mass.data, volume.data, int(volume.shape[0]),
                  self.formulae.constants.rho_w)
 
@@ -426,12 +440,57 @@ def backend_class_for(engine_getter, name, doc=None):  # pylint: disable=too-man
                 multiplier=solver["multiplier"], RH_rtol=solver["RH_rtol"],
                 max_iters=solver["max_iters"])
 
+        # ---- freezing (freezing_methods.py; include/sdm_freezing.h) -------------------------------
+        def freeze_singular(self, *, attributes, temperature, relative_humidity, cell, thaw):
+            frz.check_formulae(self.formulae)
+            mass = attributes.signed_water_mass
+            self.engine.call_freezing(
+                "sdm_freeze_singular", mass.data, attributes.freezing_temperature.data,
+                temperature.data, relative_humidity.data, cell.data, int(mass.shape[0]),
+                int(bool(thaw)), frz.constants_of(self.formulae))
+
+        def freeze_time_dependent(self, *, rand, attributes, timestep, cell, a_w_ice,
+                                  temperature, relative_humidity, thaw):
+            frz.check_formulae(self.formulae)
+            mass = attributes.signed_water_mass
+            self.engine.call_freezing(
+                "sdm_freeze_time_dependent", rand.data, mass.data,
+                attributes.immersed_surface_area.data, float(timestep), cell.data, a_w_ice.data,
+                temperature.data, relative_humidity.data, int(mass.shape[0]), int(bool(thaw)),
+                frz.j_het_code(self.formulae), frz.constants_of(self.formulae))
+
+        def freeze_time_dependent_homogeneous(self, *, rand, attributes, timestep, cell, a_w_ice,
+                                              temperature, relative_humidity_ice, thaw):
+            frz.check_formulae(self.formulae)
+            mass = attributes.signed_water_mass
+            self.engine.call_freezing(
+                "sdm_freeze_time_dependent_homogeneous", rand.data, mass.data,
+                attributes.volume.data, float(timestep), cell.data, a_w_ice.data,
+                temperature.data, relative_humidity_ice.data, int(mass.shape[0]),
+                int(bool(thaw)), frz.j_hom_code(self.formulae), frz.constants_of(self.formulae))
+
+        def record_freezing_temperatures(self, *, data, cell_id, temperature,
+                                         signed_water_mass):
+            self.engine.call_freezing(
+                "sdm_record_freezing_temperatures", data.data, cell_id.data, temperature.data,
+                signed_water_mass.data, int(data.shape[0]))
+
+        def a_w_ice(self, *, T, p, RH, water_vapour_mixing_ratio, a_w_ice, RH_ice):
+            self.engine.call_freezing(
+                "sdm_a_w_ice", T.data, p.data, RH.data, water_vapour_mixing_ratio.data,
+                a_w_ice.data, RH_ice.data, int(T.shape[0]), frz.constants_of(self.formulae))
+
         # ---- ambient thermodynamics (physics_methods.py) ----------------------------------------
+        def _ambient_consts(self):
+            # (these methods do not depend on the particle shape: Moist calls them under
+            # MixedPhaseSpheres too, where the condensation solver itself stays refused)
+            return constants_of(self.formulae, mixed_phase=self._mixed_phase())
+
         def temperature_pressure_rh(self, *, rhod, thd, water_vapour_mixing_ratio, T, p, RH):
             self.engine.call_condensation(
                 "sdm_temperature_pressure_rh", rhod.data, thd.data,
                 water_vapour_mixing_ratio.data, T.data, p.data, RH.data, int(T.shape[0]),
-                constants_of(self.formulae))
+                self._ambient_consts())
 
         def air_density(self, *, output, rhod, water_vapour_mixing_ratio):
             self.engine.call_condensation("sdm_air_density", output.data, rhod.data,
@@ -440,12 +499,12 @@ def backend_class_for(engine_getter, name, doc=None):  # pylint: disable=too-man
         def air_dynamic_viscosity(self, *, output, temperature):
             self.engine.call_condensation("sdm_air_dynamic_viscosity", output.data,
                                           temperature.data, int(output.shape[0]),
-                                          constants_of(self.formulae))
+                                          self._ambient_consts())
 
         def critical_volume(self, *, v_cr, kappa, f_org, v_dry, v_wet, T, cell):
             self.engine.call_condensation(
                 "sdm_critical_volume", v_cr.data, kappa.data, f_org.data, v_dry.data, v_wet.data,
-                T.data, cell.data, int(v_cr.shape[0]), constants_of(self.formulae))
+                T.data, cell.data, int(v_cr.shape[0]), self._ambient_consts())
 
         def reynolds_number(self, *, output, cell_id, dynamic_viscosity, density, radius,
                             velocity_wrt_air):

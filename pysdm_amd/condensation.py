@@ -34,22 +34,32 @@ def _option_name(value):
     return getattr(value, "__name__", type(value).__name__)
 
 
+def _check_option(formulae, option):
+    default = REQUIRED_OPTIONS[option]
+    value = getattr(formulae, option, None)
+    if value is None:
+        raise NotImplementedError(f"condensation: formulae lack `{option}`")
+    name = _option_name(value)
+    if name != default:
+        raise NotImplementedError(
+            f"condensation on this backend supports {option}={default!r} only, "
+            f"not {name!r}")
+
+
 def check_formulae(formulae):
     """refuses every formulae choice other than PySDM's default on the condensation path"""
-    for option, default in REQUIRED_OPTIONS.items():
-        value = getattr(formulae, option, None)
-        if value is None:
-            raise NotImplementedError(f"condensation: formulae lack `{option}`")
-        name = _option_name(value)
-        if name != default:
-            raise NotImplementedError(
-                f"condensation on this backend supports {option}={default!r} only, "
-                f"not {name!r}")
+    for option in REQUIRED_OPTIONS:
+        _check_option(formulae, option)
 
 
-def constants_of(formulae):
-    """`formulae.constants` as the `consts` array of include/sdm_condensation.h"""
-    check_formulae(formulae)
+def constants_of(formulae, mixed_phase=False):
+    """`formulae.constants` as the `consts` array of include/sdm_condensation.h (`mixed_phase`:
+    for the ambient methods, which do not depend on the particle shape, under MixedPhaseSpheres)"""
+    if mixed_phase:
+        for option in CONDENSATION_DEFAULTS:
+            _check_option(formulae, option)
+    else:
+        check_formulae(formulae)
     k = formulae.constants
     return [float(getattr(k, name)) for name in CONSTANT_NAMES]
 
@@ -102,7 +112,10 @@ class AmbientColumns:  # pylint: disable=too-few-public-methods,too-many-instanc
     """per-cell ambient state of a Population: rhod, thd, qv (water vapour mixing ratio), their
     predicted values, air density and air dynamic viscosity (engine arrays of n_cell)"""
 
-    def __init__(self, engine, formulae, *, rhod, thd, qv, prhod=None, pthd=None, pqv=None):
+    def __init__(self, engine, formulae, *, rhod, thd, qv, prhod=None, pthd=None, pqv=None,
+                 mixed_phase=False):
+        """`mixed_phase`: also keeps a_w_ice and RH_ice (what PySDM's `Moist` does with
+        `mixed_phase=True`, environments/impl/moist.py:12-14,80-88), for pysdm_amd.freezing"""
         up = engine.upload
         as_f = lambda v: np.asarray(v, dtype=float)  # noqa: E731
         self.engine, self.formulae = engine, formulae
@@ -114,15 +127,23 @@ class AmbientColumns:  # pylint: disable=too-few-public-methods,too-many-instanc
         self.T, self.p, self.RH = (engine.empty(n_cell, FLOAT) for _ in range(3))
         self.air_density = engine.empty(n_cell, FLOAT)
         self.air_dynamic_viscosity = engine.empty(n_cell, FLOAT)
+        self.mixed_phase = bool(mixed_phase)
+        if self.mixed_phase:
+            self.a_w_ice, self.RH_ice = engine.empty(n_cell, FLOAT), engine.empty(n_cell, FLOAT)
         self.update()
 
     def update(self):
         """T, p, RH, air density and viscosity from rhod / thd / qv (Moist.sync,
         environments/impl/moist.py:60-100)"""
         eng, n = self.engine, self.engine.size(self.rhod)
-        consts = constants_of(self.formulae)
+        consts = constants_of(self.formulae, mixed_phase=self.mixed_phase)
         eng.call_condensation("sdm_temperature_pressure_rh", self.rhod, self.thd, self.qv, self.T,
                               self.p, self.RH, n, consts)
+        if self.mixed_phase:
+            from . import freezing  # pylint: disable=import-outside-toplevel
+
+            eng.call_freezing("sdm_a_w_ice", self.T, self.p, self.RH, self.qv, self.a_w_ice,
+                              self.RH_ice, n, freezing.constants_of(self.formulae))
         eng.call_condensation("sdm_air_density", self.air_density, self.rhod, self.qv, n)
         eng.call_condensation("sdm_air_dynamic_viscosity", self.air_dynamic_viscosity, self.T, n,
                               consts)

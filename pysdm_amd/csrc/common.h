@@ -272,6 +272,10 @@ __host__ __device__ __forceinline__ double pcg_output(u128 state) {
   return (double)(v >> 11) * (1.0 / 9007199254740992.0);
 }
 
+// consecutive draws per thread of the kernels that walk the stream (ctx.hip: k_pcg_fill;
+// freezing.hip: k_freezing_step)
+#define PCG_ELEMS 4
+
 #define PCG_AFF_SMALL 4097
 #define PCG_AFF_TILES 8192
 #define PCG_AFF_STRIDE 4096

@@ -329,7 +329,6 @@ u128 sdm_pcg_advance_host(u128 state, u128 inc, uint64_t delta) {
   return acc_mult * state + acc_plus;
 }
 
-#define PCG_ELEMS 4
 // out[i] = draw number (offset + i); `s_off` = generator state after `offset` draws
 __global__ void __launch_bounds__(SDM_BLOCK)
 k_pcg_fill(double *__restrict__ out, int64_t n, u128 s_off, u128 inc,

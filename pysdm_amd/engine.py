@@ -23,6 +23,8 @@ class Engine:
     handle = None
     # the implementation of include/sdm_condensation.h that goes with `library` (same contexts)
     condensation_library = None
+    # likewise include/sdm_freezing.h
+    freezing_library = None
 
     # ---- arrays -----------------------------------------------------------------------------
     def empty(self, shape, dtype):
@@ -70,6 +72,13 @@ class Engine:
         self._before_call()
         self.condensation_library.invoke(symbol, self.handle, args)
 
+    def call_freezing(self, symbol, *args):
+        """a symbol of include/sdm_freezing.h"""
+        if self.freezing_library is None:
+            raise NotImplementedError(f"engine `{self.name}` has no freezing library")
+        self._before_call()
+        self.freezing_library.invoke(symbol, self.handle, args)
+
     def _before_call(self):
         pass
 
@@ -95,6 +104,7 @@ class HipEngine(Engine):
         self.torch = torch
         self.library = abi.hip_library()
         self.condensation_library = abi.condensation_library()
+        self.freezing_library = abi.freezing_library()
         self.handle = abi.c_ptr()
         self.library.check(self.library.cdll.sdm_ctx_create(ctypes.byref(self.handle),
                                                             abi.c_int(device_index)))

@@ -3,8 +3,12 @@ stand-in for PySDM's own where PySDM is absent; under PySDM the real one is pass
 
 Collision-path subset of PySDM/formulae.py:27-67 (same keyword names: `seed`, `constants`,
 `terminal_velocity`, `fragmentation_function`, `handle_all_breakups`,
-`particle_shape_and_density`, `particle_advection`); everything unrelated to the path is absent.
+`particle_shape_and_density`, `particle_advection`), the options of the condensation path (defaults
+only) and of the freezing path (`particle_shape_and_density="MixedPhaseSpheres"`,
+`heterogeneous_ice_nucleation_rate`, `homogeneous_ice_nucleation_rate`); everything unrelated to
+these paths is absent.
 """
+import math
 from types import SimpleNamespace
 
 import numpy as np
@@ -26,6 +30,19 @@ CONDENSATION_DEFAULTS = {
     "state_variable_triplet": "LibcloudphPlusPlus",
     "air_dynamic_viscosity": "ZografosEtAl1987",
 }
+# the choices the freezing path implements (pysdm_amd/freezing.py), PySDM's default first, and
+# the constants each needs to be finite (as the reference's classes assert when instantiated)
+FREEZING_OPTIONS = {
+    "heterogeneous_ice_nucleation_rate": ("Null", "Constant", "ABIFM"),
+    "homogeneous_ice_nucleation_rate": ("Null", "Constant", "Koop2000", "Koop_Correction",
+                                        "KoopMurray2016"),
+}
+_FINITE = {
+    ("heterogeneous_ice_nucleation_rate", "Constant"): ("J_HET",),
+    ("heterogeneous_ice_nucleation_rate", "ABIFM"): ("ABIFM_M", "ABIFM_C"),
+    ("homogeneous_ice_nucleation_rate", "Constant"): ("J_HOM",),
+}
+PARTICLE_SHAPES = ("LiquidSpheres", "MixedPhaseSpheres")
 
 
 class _Trivia:  # PySDM/physics/trivia.py:19-28
@@ -52,6 +69,23 @@ class _LiquidSpheres:  # PySDM/physics/particle_shape_and_density/liquid_spheres
     @staticmethod
     def volume_to_mass(volume):
         return _const.rho_w * volume
+
+
+class _MixedPhaseSpheres:  # PySDM/physics/particle_shape_and_density/mixed_phase_spheres.py
+    __name__ = "MixedPhaseSpheres"
+
+    def __init__(self, constants):
+        self._rho_w, self._rho_i = constants.rho_w, constants.rho_i
+
+    @staticmethod
+    def supports_mixed_phase(_=None):
+        return True
+
+    def mass_to_volume(self, mass):
+        return np.maximum(0.0, mass) / self._rho_w + np.minimum(0.0, mass) / self._rho_i
+
+    def volume_to_mass(self, volume):
+        return np.maximum(0.0, volume) * self._rho_w + np.minimum(0.0, volume) * self._rho_i
 
 
 class _ImplicitInSpace:  # PySDM/physics/particle_advection/implicit_in_space.py:11-13
@@ -84,10 +118,13 @@ class Formulae:  # pylint: disable=too-few-public-methods,too-many-arguments
         terminal_velocity="GunnKinzer1949",
         handle_all_breakups=False,
         particle_advection="ImplicitInSpace",
+        heterogeneous_ice_nucleation_rate="Null",
+        homogeneous_ice_nucleation_rate="Null",
         **condensation_options,
     ):
-        if particle_shape_and_density != "LiquidSpheres":
-            raise NotImplementedError(particle_shape_and_density)
+        if particle_shape_and_density not in PARTICLE_SHAPES:
+            raise NotImplementedError(
+                f"particle_shape_and_density={particle_shape_and_density!r}")
         # the condensation path supports PySDM's defaults only (pysdm_amd/condensation.py)
         for option, value in condensation_options.items():
             if option not in CONDENSATION_DEFAULTS:
@@ -110,7 +147,20 @@ class Formulae:  # pylint: disable=too-few-public-methods,too-many-arguments
         self.fragmentation_function = fragmentation_function
         self.handle_all_breakups = handle_all_breakups
         self.trivia = _Trivia()
-        self.particle_shape_and_density = _LiquidSpheres()
+        if particle_shape_and_density == "MixedPhaseSpheres":
+            self.particle_shape_and_density = _MixedPhaseSpheres(self.constants)
+        else:
+            self.particle_shape_and_density = _LiquidSpheres()
+        for option, value in (
+                ("heterogeneous_ice_nucleation_rate", heterogeneous_ice_nucleation_rate),
+                ("homogeneous_ice_nucleation_rate", homogeneous_ice_nucleation_rate)):
+            if value not in FREEZING_OPTIONS[option]:
+                raise NotImplementedError(f"{option}={value!r}")
+            for name in _FINITE.get((option, value), ()):
+                if not math.isfinite(getattr(self.constants, name)):
+                    raise ValueError(f"{option}={value!r} needs the constant {name} "
+                                     f"(pass constants={{'{name}': ...}})")
+            setattr(self, option, SimpleNamespace(__name__=value))
         self.terminal_velocity = terminal_velocity
         schemes = {"ImplicitInSpace": _ImplicitInSpace, "ExplicitInSpace": _ExplicitInSpace}
         if particle_advection not in schemes:

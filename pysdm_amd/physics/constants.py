@@ -91,6 +91,43 @@ ZOGRAFOS_1987_COEFF_T2 = -1.4346e-11
 ZOGRAFOS_1987_COEFF_T1 = 5.0523e-08
 ZOGRAFOS_1987_COEFF_T0 = 4.113e-06
 
+# freezing path (pysdm_amd/freezing.py): ice density, the Flatau-Walko-Cotton coefficients of the
+# saturation vapour pressure over ice (Flatau et al. 1992, in Pa), ABIFM (Knopf & Alpert 2013: M
+# and C depend on the ice nucleus and have no default), the homogeneous rates of Koop et al. 2000,
+# its correction by Spichtinger et al. 2023 and Koop & Murray 2016 (tab. VII); the constant rates
+# J_HET / J_HOM have no default either (PySDM/physics/constants_defaults.py:139-155,188,312-356,
+# written as the doubles it arrives at)
+rho_i = 916.8
+FWC_I0 = 609.868993
+FWC_I1 = 49.9320233
+FWC_I2 = 1.84672631
+FWC_I3 = 0.0402737184
+FWC_I4 = 0.000565392987
+FWC_I5 = 5.216939329999999e-06
+FWC_I6 = 3.0783958300000004e-08
+FWC_I7 = 1.0578516000000001e-10
+FWC_I8 = 1.61444444e-13
+J_HET = math.nan
+J_HOM = math.nan
+ABIFM_M = math.inf
+ABIFM_C = math.inf
+ABIFM_UNIT = 10000.0
+KOOP_2000_C1 = -906.7
+KOOP_2000_C2 = 8502
+KOOP_2000_C3 = -26924
+KOOP_2000_C4 = 29180
+KOOP_CORR = -1.522
+KOOP_UNIT = 999999.9999999999
+KOOP_MIN_DA_W_ICE = 0.26
+KOOP_MAX_DA_W_ICE = 0.34
+KOOP_MURRAY_C0 = -3020.684
+KOOP_MURRAY_C1 = -425.921
+KOOP_MURRAY_C2 = -25.9779
+KOOP_MURRAY_C3 = -0.868451
+KOOP_MURRAY_C4 = -0.0166203
+KOOP_MURRAY_C5 = -0.000171736
+KOOP_MURRAY_C6 = -7.46953e-07
+
 
 def namespace(overrides=None):
     """the numeric constants of this module as one namespace, optionally with overrides"""
