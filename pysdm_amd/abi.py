@@ -24,6 +24,8 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "sdm_hip.h")
 CONDENSATION_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "sdm_condensation.h")
 # and so has the freezing path
 FREEZING_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "sdm_freezing.h")
+# and the vapour-deposition path
+DEPOSITION_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "sdm_deposition.h")
 # SDM_HIP_LIB: another build of the same library (tuning variants); still no fallback
 HIP_LIB_PATH = os.environ.get("SDM_HIP_LIB") or os.path.join(_HERE, "libsdm_hip.so")
 
@@ -114,6 +116,14 @@ class FreezingCfg(ctypes.Structure):  # == sdm_freezing_cfg (include/sdm_freezin
         ("homogeneous_freezing", ctypes.c_int32), ("thaw", ctypes.c_int32),
         ("j_het", ctypes.c_int32), ("j_hom", ctypes.c_int32), ("rates", ctypes.c_int32),
         ("reserved", ctypes.c_int32), ("timestep", c_f64), ("rng_state_inc", c_u64 * 4),
+    ]
+
+
+class DepositionCfg(ctypes.Structure):  # == sdm_deposition_cfg (include/sdm_deposition.h)
+    _fields_ = [
+        ("coordinate", ctypes.c_int32), ("capacity", ctypes.c_int32),
+        ("kinetics", ctypes.c_int32), ("sum", ctypes.c_int32),
+        ("time_step", c_f64), ("cell_volume", c_f64),
     ]
 
 
@@ -259,6 +269,7 @@ class Library:
 _hip_library = None
 _condensation_library = None
 _freezing_library = None
+_deposition_library = None
 
 
 def hip_library():
@@ -285,6 +296,15 @@ def freezing_library():
         _freezing_library = Library(HIP_LIB_PATH, "the HIP kernels of pysdm_amd",
                                     header=FREEZING_HEADER_PATH)
     return _freezing_library
+
+
+def deposition_library():
+    """libsdm_hip.so bound to include/sdm_deposition.h (same file, same contexts)"""
+    global _deposition_library  # pylint: disable=global-statement
+    if _deposition_library is None:
+        _deposition_library = Library(HIP_LIB_PATH, "the HIP kernels of pysdm_amd",
+                                      header=DEPOSITION_HEADER_PATH)
+    return _deposition_library
 
 
 def pcg64_state_inc(seed):

@@ -17,6 +17,7 @@ import warnings
 import numpy as np
 
 from ..abi import pcg64_state_inc
+from .. import deposition as dep
 from .. import freezing as frz
 from ..condensation import check_formulae, condensation_call, constants_of
 from ..displacement import SCHEMES
@@ -479,6 +480,37 @@ def backend_class_for(engine_getter, name, doc=None):  # pylint: disable=too-man
             self.engine.call_freezing(
                 "sdm_a_w_ice", T.data, p.data, RH.data, water_vapour_mixing_ratio.data,
                 a_w_ice.data, RH_ice.data, int(T.shape[0]), frz.constants_of(self.formulae))
+
+        # ---- vapour deposition on ice (deposition_methods.py; include/sdm_deposition.h) ----------
+        def deposition(self, *, multiplicity, signed_water_mass, current_temperature,
+                       current_total_pressure, current_relative_humidity,
+                       current_water_activity, current_vapour_mixing_ratio,
+                       current_dry_air_density, current_dry_potential_temperature, cell_volume,
+                       time_step, cell_id, reynolds_number, schmidt_number,
+                       predicted_vapour_mixing_ratio, predicted_dry_potential_temperature):
+            # pylint: disable=unused-argument,too-many-locals
+            # (reynolds_number, schmidt_number: not read by the reference either - both
+            # ventilation factors are the literal 1)
+            if not self._mixed_phase():  # deposition_methods.py:14
+                raise NotImplementedError(
+                    "deposition needs particle_shape_and_density='MixedPhaseSpheres'")
+            if (predicted_vapour_mixing_ratio is current_vapour_mixing_ratio
+                    or predicted_dry_potential_temperature is current_dry_potential_temperature):
+                raise ValueError("deposition: a predicted Storage is the current one (the "
+                                 "reference's serial loop over aliased arrays is not reproduced)")
+            cfg = dep.deposition_cfg(self.formulae, time_step, cell_volume)  # SDM_DEP_SUM_ORDERED
+            eng = self.engine
+            n_exceeded = eng.zeros(1, np.int64)
+            eng.call_deposition(
+                "sdm_deposition", cfg, int(signed_water_mass.shape[0]),
+                int(current_temperature.shape[0]), multiplicity.data, signed_water_mass.data,
+                cell_id.data, current_temperature.data, current_total_pressure.data,
+                current_relative_humidity.data, current_water_activity.data,
+                current_vapour_mixing_ratio.data, current_dry_air_density.data,
+                current_dry_potential_temperature.data, predicted_vapour_mixing_ratio.data,
+                predicted_dry_potential_temperature.data, n_exceeded,
+                dep.constants_of(self.formulae))
+            dep.raise_if_exceeded(int(np.asarray(eng.download(n_exceeded))[0]))
 
         # ---- ambient thermodynamics (physics_methods.py) ----------------------------------------
         def _ambient_consts(self):

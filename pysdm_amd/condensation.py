@@ -57,7 +57,9 @@ def constants_of(formulae, mixed_phase=False):
     for the ambient methods, which do not depend on the particle shape, under MixedPhaseSpheres)"""
     if mixed_phase:
         for option in CONDENSATION_DEFAULTS:
-            _check_option(formulae, option)
+            # (no ambient method reads the coordinate, which deposition lets be "WaterMass")
+            if option != "diffusion_coordinate":
+                _check_option(formulae, option)
     else:
         check_formulae(formulae)
     k = formulae.constants

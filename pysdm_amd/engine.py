@@ -25,6 +25,8 @@ class Engine:
     condensation_library = None
     # likewise include/sdm_freezing.h
     freezing_library = None
+    # likewise include/sdm_deposition.h
+    deposition_library = None
 
     # ---- arrays -----------------------------------------------------------------------------
     def empty(self, shape, dtype):
@@ -79,6 +81,13 @@ class Engine:
         self._before_call()
         self.freezing_library.invoke(symbol, self.handle, args)
 
+    def call_deposition(self, symbol, *args):
+        """a symbol of include/sdm_deposition.h"""
+        if self.deposition_library is None:
+            raise NotImplementedError(f"engine `{self.name}` has no deposition library")
+        self._before_call()
+        self.deposition_library.invoke(symbol, self.handle, args)
+
     def _before_call(self):
         pass
 
@@ -105,6 +114,7 @@ class HipEngine(Engine):
         self.library = abi.hip_library()
         self.condensation_library = abi.condensation_library()
         self.freezing_library = abi.freezing_library()
+        self.deposition_library = abi.deposition_library()
         self.handle = abi.c_ptr()
         self.library.check(self.library.cdll.sdm_ctx_create(ctypes.byref(self.handle),
                                                             abi.c_int(device_index)))

@@ -5,8 +5,9 @@ Collision-path subset of PySDM/formulae.py:27-67 (same keyword names: `seed`, `c
 `terminal_velocity`, `fragmentation_function`, `handle_all_breakups`,
 `particle_shape_and_density`, `particle_advection`), the options of the condensation path (defaults
 only) and of the freezing path (`particle_shape_and_density="MixedPhaseSpheres"`,
-`heterogeneous_ice_nucleation_rate`, `homogeneous_ice_nucleation_rate`); everything unrelated to
-these paths is absent.
+`heterogeneous_ice_nucleation_rate`, `homogeneous_ice_nucleation_rate`) and of vapour deposition on
+ice (`diffusion_ice_capacity`, `diffusion_ice_kinetics`, `latent_heat_sublimation`,
+`diffusion_coordinate="WaterMass"`); everything unrelated to these paths is absent.
 """
 import math
 from types import SimpleNamespace
@@ -43,6 +44,15 @@ _FINITE = {
     ("homogeneous_ice_nucleation_rate", "Constant"): ("J_HOM",),
 }
 PARTICLE_SHAPES = ("LiquidSpheres", "MixedPhaseSpheres")
+# the choices the deposition path implements (pysdm_amd/deposition.py), PySDM's default first.
+# `diffusion_coordinate` is shared with condensation, which implements the logarithm only
+# (condensation.check_formulae goes on refusing "WaterMass")
+DEPOSITION_OPTIONS = {
+    "diffusion_ice_capacity": ("Spherical", "Columnar"),
+    "diffusion_ice_kinetics": ("Standard", "Neglect"),
+    "latent_heat_sublimation": ("MurphyKoop2005",),
+}
+DIFFUSION_COORDINATES = ("WaterMassLogarithm", "WaterMass")
 
 
 class _Trivia:  # PySDM/physics/trivia.py:19-28
@@ -120,6 +130,9 @@ class Formulae:  # pylint: disable=too-few-public-methods,too-many-arguments
         particle_advection="ImplicitInSpace",
         heterogeneous_ice_nucleation_rate="Null",
         homogeneous_ice_nucleation_rate="Null",
+        diffusion_ice_capacity="Spherical",
+        diffusion_ice_kinetics="Standard",
+        latent_heat_sublimation="MurphyKoop2005",
         **condensation_options,
     ):
         if particle_shape_and_density not in PARTICLE_SHAPES:
@@ -129,9 +142,18 @@ class Formulae:  # pylint: disable=too-few-public-methods,too-many-arguments
         for option, value in condensation_options.items():
             if option not in CONDENSATION_DEFAULTS:
                 raise TypeError(f"Formulae got an unexpected keyword argument '{option}'")
+            if option == "diffusion_coordinate" and value in DIFFUSION_COORDINATES:
+                continue
             if value != CONDENSATION_DEFAULTS[option]:
                 raise NotImplementedError(f"{option}={value!r}")
         for option, value in CONDENSATION_DEFAULTS.items():
+            setattr(self, option,
+                    SimpleNamespace(__name__=condensation_options.get(option, value)))
+        for option, value in (("diffusion_ice_capacity", diffusion_ice_capacity),
+                              ("diffusion_ice_kinetics", diffusion_ice_kinetics),
+                              ("latent_heat_sublimation", latent_heat_sublimation)):
+            if value not in DEPOSITION_OPTIONS[option]:
+                raise NotImplementedError(f"{option}={value!r}")
             setattr(self, option, SimpleNamespace(__name__=value))
         if terminal_velocity not in ("GunnKinzer1949", "RogersYau", "PowerSeries"):
             raise NotImplementedError(terminal_velocity)

@@ -128,6 +128,29 @@ KOOP_MURRAY_C4 = -0.0166203
 KOOP_MURRAY_C5 = -0.000171736
 KOOP_MURRAY_C6 = -7.46953e-07
 
+# vapour deposition on ice (pysdm_amd/deposition.py): molar mass of water, the latent heat of
+# sublimation of Murphy & Koop 2005 (eq. 5, J / mol), the mean free path of vapour in air at
+# T_STP / p_STP and the Cunningham factor of the transition-regime correction (Pruppacher & Klett
+# 2010), mass and heat accommodation coefficients of ice, the capacity of columnar crystals of
+# Spichtinger et al. 2023 (eq. A11-A12) (PySDM/physics/constants_defaults.py:87-107,227,277-290,
+# 532-538, written as the doubles it arrives at)
+Mv = 0.018015270337240392
+MK05_SUB_C1 = 46782.5
+MK05_SUB_C2 = 35.8925
+MK05_SUB_C3 = 0.07414
+MK05_SUB_C4 = 541.5
+MK05_SUB_C5 = 123.75
+lmbd_w_0 = 6.6e-08
+T_STP = 288.15
+p_STP = 101325.0
+C_cunn = 0.7
+MAC_ice = 0.5
+HAC_ice = 1.0
+capacity_columnar_ice_A1 = 0.015755
+capacity_columnar_ice_B1 = 0.3
+capacity_columnar_ice_A2 = 0.33565
+capacity_columnar_ice_B2 = 0.43
+
 
 def namespace(overrides=None):
     """the numeric constants of this module as one namespace, optionally with overrides"""
