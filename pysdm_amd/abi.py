@@ -26,6 +26,8 @@ CONDENSATION_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "sdm_
 FREEZING_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "sdm_freezing.h")
 # and the vapour-deposition path
 DEPOSITION_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "sdm_deposition.h")
+# and the aqueous-chemistry path
+CHEMISTRY_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "sdm_chemistry.h")
 # SDM_HIP_LIB: another build of the same library (tuning variants); still no fallback
 HIP_LIB_PATH = os.environ.get("SDM_HIP_LIB") or os.path.join(_HERE, "libsdm_hip.so")
 
@@ -127,6 +129,14 @@ class DepositionCfg(ctypes.Structure):  # == sdm_deposition_cfg (include/sdm_dep
     ]
 
 
+class ChemistryCfg(ctypes.Structure):  # == sdm_chemistry_cfg (include/sdm_chemistry.h)
+    _fields_ = [
+        ("n_substep", ctypes.c_int32), ("system_type", ctypes.c_int32), ("sum", ctypes.c_int32),
+        ("constants", ctypes.c_int32), ("timestep", c_f64), ("cell_volume", c_f64),
+        ("H_min", c_f64), ("H_max", c_f64), ("ionic_strength_threshold", c_f64), ("rtol", c_f64),
+    ]
+
+
 # ---- header parsing -------------------------------------------------------------------------
 _SCALARS = {"int": c_int, "int64_t": c_i64, "uint64_t": c_u64, "double": c_f64,
             "int32_t": ctypes.c_int32}
@@ -135,7 +145,7 @@ _ELEMENT = {"double": (np.float64,), "int64_t": (np.int64,), "uint8_t": (np.uint
 
 
 class Param:  # pylint: disable=too-few-public-methods
-    """one C parameter: kind in {ctx, scalar, pointer, host_array}"""
+    """one C parameter: kind in {ctx, scalar, pointer, host_array, pointer_array}"""
 
     def __init__(self, text):
         text = " ".join(text.split())
@@ -151,7 +161,8 @@ class Param:  # pylint: disable=too-few-public-methods
         if self.base == "sdm_ctx":
             self.kind = "ctx" if stars == 1 else "pointer"
         elif self.array_len is not None:
-            self.kind = "host_array"
+            # `double *const moles[7]`: a host array of pointers to columns
+            self.kind = "pointer_array" if stars else "host_array"
         elif stars:
             self.kind = "pointer"
         else:
@@ -162,6 +173,8 @@ class Param:  # pylint: disable=too-few-public-methods
             return _SCALARS[self.base](value)
         if self.kind == "host_array":
             return _host_array(value, self, symbol)
+        if self.kind == "pointer_array":
+            return _pointer_array(value, self, symbol)
         return _pointer(value, self, symbol)
 
 
@@ -173,6 +186,22 @@ def _host_array(value, param, symbol):
         raise ValueError(f"{symbol}: `{param.name}` takes {param.array_len} values, "
                          f"got {len(values)}")
     return (_SCALARS[param.base] * len(values))(*values)
+
+
+def _pointer_array(value, param, symbol):
+    """a host array of column pointers, every column checked like a single pointer parameter"""
+    columns = list(value)
+    if len(columns) != param.array_len:
+        raise ValueError(f"{symbol}: `{param.name}` takes {param.array_len} columns, "
+                         f"got {len(columns)}")
+    out = (c_ptr * len(columns))()
+    for at, column in enumerate(columns):
+        if column is None:
+            raise ValueError(f"{symbol}: `{param.name}[{at}]` is missing")
+        pointer = _pointer(column, param, symbol)
+        out[at] = pointer.value if isinstance(pointer, c_ptr) else ctypes.cast(
+            pointer, c_ptr).value
+    return out
 
 
 def _pointer(value, param, symbol):
@@ -213,7 +242,7 @@ def parse_header(path=HEADER_PATH):
     text = re.sub(r"//[^\n]*", " ", text)
     table = {}
     for ret, name, params in re.findall(
-            r"\b(int|const char \*)\s*(sdm_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text):
+            r"\b(int|const char \*)\s*(sdm_[A-Za-z0-9_]+)\s*\(([^()]*)\)\s*;", text):
         params = params.strip()
         plist = [] if params in ("", "void") else [Param(p) for p in params.split(",")]
         table[name] = ("str" if "char" in ret else "int", plist)
@@ -270,6 +299,7 @@ _hip_library = None
 _condensation_library = None
 _freezing_library = None
 _deposition_library = None
+_chemistry_library = None
 
 
 def hip_library():
@@ -305,6 +335,15 @@ def deposition_library():
         _deposition_library = Library(HIP_LIB_PATH, "the HIP kernels of pysdm_amd",
                                       header=DEPOSITION_HEADER_PATH)
     return _deposition_library
+
+
+def chemistry_library():
+    """libsdm_hip.so bound to include/sdm_chemistry.h (same file, same contexts)"""
+    global _chemistry_library  # pylint: disable=global-statement
+    if _chemistry_library is None:
+        _chemistry_library = Library(HIP_LIB_PATH, "the HIP kernels of pysdm_amd",
+                                     header=CHEMISTRY_HEADER_PATH)
+    return _chemistry_library
 
 
 def pcg64_state_inc(seed):

@@ -17,6 +17,7 @@ import warnings
 import numpy as np
 
 from ..abi import pcg64_state_inc
+from .. import chemistry as chem
 from .. import deposition as dep
 from .. import freezing as frz
 from ..condensation import check_formulae, condensation_call, constants_of
@@ -511,6 +512,136 @@ def backend_class_for(engine_getter, name, doc=None):  # pylint: disable=too-man
                 predicted_dry_potential_temperature.data, n_exceeded,
                 dep.constants_of(self.formulae))
             dep.raise_if_exceeded(int(np.asarray(eng.download(n_exceeded))[0]))
+
+        # ---- aqueous chemistry (chemistry_methods.py; include/sdm_chemistry.h) -------------------
+        # {gas: g / mol} replacing entries of pysdm_amd.chemistry.MOLAR_MASS (e.g. chempy's values)
+        chemistry_molar_mass = None
+
+        def _chem_checked(self):
+            """the validated constants table, built once per (formulae, molar masses)"""
+            key = (id(self.formulae), id(self.chemistry_molar_mass))
+            cached = getattr(self, "_chem_cache", None)
+            if cached is None or cached[0] != key:
+                table = chem.check_formulae(self.formulae, self.chemistry_molar_mass)
+                cached = self._chem_cache = (key, table, list(table.values()))
+            return cached
+
+        def _chem_consts(self):
+            return self._chem_checked()[2]
+
+        def _chem_table(self, names, prefix, dT_prefix, kinetic=False):
+            table = self._chem_checked()[1]
+            return {name: chem.TemperatureDependent(table, table[prefix + name],
+                                                    table[dT_prefix + name], kinetic)
+                    for name in names}
+
+        # what AqueousChemistry.register and `dissolution` read from the backend, with the
+        # reference's keys (ChemistryMethods.__init__, chemistry_methods.py:37-42)
+        @property
+        def KINETIC_CONST(self):
+            from types import SimpleNamespace  # pylint: disable=import-outside-toplevel
+
+            return SimpleNamespace(KINETIC_CONST=self._chem_table(chem.KINETIC, "", "dT_", True))
+
+        @property
+        def EQUILIBRIUM_CONST(self):
+            from types import SimpleNamespace  # pylint: disable=import-outside-toplevel
+
+            return SimpleNamespace(
+                EQUILIBRIUM_CONST=self._chem_table(chem.EQUILIBRIUM, "", "dT_"))
+
+        @property
+        def HENRY_CONST(self):
+            from types import SimpleNamespace  # pylint: disable=import-outside-toplevel
+
+            return SimpleNamespace(
+                HENRY_CONST=self._chem_table(chem.GASES, "HENRY_", "dT_HENRY_"))
+
+        @property
+        def specific_gravities(self):
+            return chem.specific_gravities(self.formulae, self.chemistry_molar_mass)
+
+        def _chem_counts(self, *counts):
+            down = self.engine.download
+            return [int(np.asarray(down(c))[0]) for c in counts]
+
+        def chem_recalculate_cell_data(self, equilibrium_consts, kinetic_consts, temperature):
+            eng = self.engine
+            n_cell = int(temperature.shape[0])
+            henry = [eng.empty(n_cell, np.float64) for _ in chem.GASES]  # (not asked for here)
+            eng.call_chemistry(
+                "sdm_chem_recalculate_cell_data", n_cell, temperature.data,
+                [equilibrium_consts[k].data for k in chem.EQUILIBRIUM],
+                [kinetic_consts[k].data for k in chem.KINETIC], henry, self._chem_consts())
+
+        def chem_recalculate_drop_data(self, dissociation_factors, equilibrium_consts, cell_id,
+                                       pH):
+            self.engine.call_chemistry(
+                "sdm_chem_recalculate_drop_data", int(pH.shape[0]), pH.data, cell_id.data,
+                [equilibrium_consts[k].data for k in chem.EQUILIBRIUM],
+                [dissociation_factors[g].data for g in chem.GASES], self._chem_consts())
+
+        def equilibrate_H(self, *, equilibrium_consts, cell_id, conc, do_chemistry_flag, pH,
+                          H_min, H_max, ionic_strength_threshold, rtol):
+            eng = self.engine
+            cfg = chem.ChemistrySetup("open", 1, ionic_strength_threshold=ionic_strength_threshold,
+                                      pH_H_min=H_min, pH_H_max=H_max, pH_rtol=rtol).cfg(
+                                          self.formulae, 0.0, 0.0)
+            n_failed = eng.zeros(1, np.int64)
+            eng.call_chemistry(
+                "sdm_equilibrate_H", cfg, int(pH.shape[0]), cell_id.data,
+                [getattr(conc, k).data for k in chem.CONC],
+                [equilibrium_consts[k].data for k in chem.EQUILIBRIUM], pH.data,
+                do_chemistry_flag.data, n_failed, self._chem_consts())
+            chem.raise_if_counted((*self._chem_counts(n_failed), 0, 0))
+
+        def dissolution(self, *, n_cell, n_threads, cell_order, cell_start_arg, idx,
+                        do_chemistry_flag, mole_amounts, env_mixing_ratio, env_T, env_p,
+                        env_rho_d, dissociation_factors, timestep, dv, system_type,
+                        droplet_volume, multiplicity):
+            # pylint: disable=unused-argument,too-many-locals
+            # (any n_cell: the cells are independent; n_threads is the reference's own assertion)
+            if not np.array_equal(np.asarray(cell_order), np.arange(int(n_cell))):
+                raise NotImplementedError("dissolution: cell_order other than arange(n_cell)")
+            eng = self.engine
+            consts = self._chem_consts()
+            cfg = chem.ChemistrySetup(system_type, 1).cfg(self.formulae, timestep, dv)
+            data = lambda x: x.data if hasattr(x, "data") and not isinstance(x, np.ndarray) else x  # noqa: E731
+            T = data(env_T)
+            eq, kin, henry = ([eng.empty(int(n_cell), np.float64) for _ in range(n)]
+                              for n in (7, 4, 6))
+            eng.call_chemistry("sdm_chem_recalculate_cell_data", int(n_cell), T, eq, kin, henry,
+                               consts)
+            # PySDM keeps the mixing ratios as NumPy arrays keyed by compound: copied in, and
+            # copied back when the system is closed
+            ratios = [eng.upload(np.asarray(env_mixing_ratio[g], dtype=float).reshape(-1))
+                      for g in chem.GASES]
+            n_negative, n_exceeded = eng.zeros(1, np.int64), eng.zeros(1, np.int64)
+            eng.call_chemistry(
+                "sdm_dissolution", cfg, int(droplet_volume.shape[0]), int(n_cell), data(idx),
+                data(cell_start_arg), do_chemistry_flag.data,
+                [mole_amounts[k].data for k in chem.GAS_KEYS], ratios, T, data(env_p),
+                data(env_rho_d), henry, [dissociation_factors[g].data for g in chem.GASES],
+                droplet_volume.data, multiplicity.data, n_negative, n_exceeded, consts)
+            if system_type == "closed":
+                for gas, ratio in zip(chem.GASES, ratios):
+                    env_mixing_ratio[gas][...] = np.asarray(eng.download(ratio)).reshape(
+                        np.shape(env_mixing_ratio[gas]))
+            chem.raise_if_counted((0, *self._chem_counts(n_negative, n_exceeded)))
+
+        def oxidation(self, *, n_sd, cell_ids, do_chemistry_flag, k0, k1, k2, k3, K_SO2, K_HSO3,
+                      timestep, droplet_volume, pH, dissociation_factor_SO2, moles_O3,
+                      moles_H2O2, moles_S_IV, moles_S_VI):
+            # pylint: disable=too-many-locals
+            # (the symbol takes the seven equilibrium columns as the other symbols do and, as its
+            # header says, reads K_SO2 and K_HSO3 only: the other five slots are never loaded)
+            eq = [K_SO2.data] * len(chem.EQUILIBRIUM)
+            eq[chem.EQUILIBRIUM.index("K_HSO3")] = K_HSO3.data
+            self.engine.call_chemistry(
+                "sdm_oxidation", int(n_sd), cell_ids.data, do_chemistry_flag.data,
+                [k0.data, k1.data, k2.data, k3.data], eq, float(timestep), droplet_volume.data,
+                pH.data, dissociation_factor_SO2.data, moles_O3.data, moles_H2O2.data,
+                moles_S_IV.data, moles_S_VI.data, self._chem_consts())
 
         # ---- ambient thermodynamics (physics_methods.py) ----------------------------------------
         def _ambient_consts(self):

@@ -144,6 +144,9 @@ SDM_MATH_FN double sdm_log(double x) {
   return sdm_log_dd(x).hi;
 }
 
+/* log(x) / ln 10: one more rounding than log (H2pH of the chemistry path; no table of its own) */
+SDM_MATH_FN double sdm_log10(double x) { return sdm_log(x) / 2.302585092994046; }
+
 SDM_MATH_FN double sdm_log1p(double x) {
   if (x != x) return x;
   if (x < -1) return sdm_nan();

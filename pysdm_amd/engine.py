@@ -27,6 +27,8 @@ class Engine:
     freezing_library = None
     # likewise include/sdm_deposition.h
     deposition_library = None
+    # likewise include/sdm_chemistry.h
+    chemistry_library = None
 
     # ---- arrays -----------------------------------------------------------------------------
     def empty(self, shape, dtype):
@@ -88,6 +90,13 @@ class Engine:
         self._before_call()
         self.deposition_library.invoke(symbol, self.handle, args)
 
+    def call_chemistry(self, symbol, *args):
+        """a symbol of include/sdm_chemistry.h"""
+        if self.chemistry_library is None:
+            raise NotImplementedError(f"engine `{self.name}` has no chemistry library")
+        self._before_call()
+        self.chemistry_library.invoke(symbol, self.handle, args)
+
     def _before_call(self):
         pass
 
@@ -115,6 +124,7 @@ class HipEngine(Engine):
         self.condensation_library = abi.condensation_library()
         self.freezing_library = abi.freezing_library()
         self.deposition_library = abi.deposition_library()
+        self.chemistry_library = abi.chemistry_library()
         self.handle = abi.c_ptr()
         self.library.check(self.library.cdll.sdm_ctx_create(ctypes.byref(self.handle),
                                                             abi.c_int(device_index)))

@@ -7,7 +7,8 @@ Collision-path subset of PySDM/formulae.py:27-67 (same keyword names: `seed`, `c
 only) and of the freezing path (`particle_shape_and_density="MixedPhaseSpheres"`,
 `heterogeneous_ice_nucleation_rate`, `homogeneous_ice_nucleation_rate`) and of vapour deposition on
 ice (`diffusion_ice_capacity`, `diffusion_ice_kinetics`, `latent_heat_sublimation`,
-`diffusion_coordinate="WaterMass"`); everything unrelated to these paths is absent.
+`diffusion_coordinate="WaterMass"`); aqueous chemistry has no options, only `trivia` entries and
+constants; everything unrelated to these paths is absent.
 """
 import math
 from types import SimpleNamespace
@@ -63,6 +64,27 @@ class _Trivia:  # PySDM/physics/trivia.py:19-28
     @staticmethod
     def radius(volume):
         return np.power(volume / _const.PI_4_3, _const.ONE_THIRD)
+
+    # trivia.py:39-64, what the aqueous-chemistry path's host side needs (pysdm_amd/chemistry.py)
+    @staticmethod
+    def within_tolerance(error_estimate, value, rtol):
+        return error_estimate < rtol * np.abs(value)
+
+    @staticmethod
+    def H2pH(H):
+        return -np.log10(H * 1e-3)
+
+    @staticmethod
+    def pH2H(pH):
+        return np.power(10, -pH) * 1e3
+
+    @staticmethod
+    def mole_fraction_2_mixing_ratio(mole_fraction, specific_gravity):
+        return specific_gravity * mole_fraction / (1 - mole_fraction)
+
+    @staticmethod
+    def mixing_ratio_2_mole_fraction(mixing_ratio, specific_gravity):
+        return mixing_ratio / (specific_gravity + mixing_ratio)
 
 
 class _LiquidSpheres:  # PySDM/physics/particle_shape_and_density/liquid_spheres.py:9-23

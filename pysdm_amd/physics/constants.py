@@ -151,6 +151,17 @@ capacity_columnar_ice_B1 = 0.3
 capacity_columnar_ice_A2 = 0.33565
 capacity_columnar_ice_B2 = 0.43
 
+# aqueous chemistry (PySDM/physics/constants_defaults.py:31,87,293-296,772 and constants.py:67-68,
+# written as the doubles it arrives at)
+R_str = 8.31446261815324
+Md = 0.028966000000000002
+ROOM_TEMP = 298.15
+M = 1000.0
+K_H2O = 1e-08
+H_u = M / p_STP
+dT_u = 1.0
+pH_w = 7
+
 
 def namespace(overrides=None):
     """the numeric constants of this module as one namespace, optionally with overrides"""
