@@ -690,7 +690,8 @@ API void oracle_feingold1988_fragmentation(double scale, double *frag_volume,
                                            double fragtol) {
   for (int64_t i = 0; i < n; ++i) {
     const double a = 1 - rand[i] * scale / x_plus_y[i];
-    frag_volume[i] = -scale * sdm_log(a > fragtol ? a : fragtol);
+    /* Python's max(a, fragtol): a nan draw stays nan (and the limiter answers it) */
+    frag_volume[i] = -scale * sdm_log(fragtol > a ? fragtol : a);
   }
 }
 
@@ -918,7 +919,8 @@ API void oracle_exp_fragmentation(double scale, double *frag_volume, const doubl
                                   int64_t n, double tol) {
   for (int64_t i = 0; i < n; ++i) {
     const double a = 1 - rand[i];
-    frag_volume[i] = -scale * sdm_log(a > tol ? a : tol);
+    /* Python's max(a, tol): a nan draw stays nan (and the limiter answers it) */
+    frag_volume[i] = -scale * sdm_log(tol > a ? tol : a);
   }
 }
 

@@ -616,7 +616,7 @@ k_exp_fragmentation(double *__restrict__ n_fragment, double scale,
   const int64_t i = TID();
   if (i >= n) return;
   const double a = 1 - rand[i];
-  double fv = -scale * sdm_log(a > tol ? a : tol);
+  double fv = -scale * sdm_log(PYMAX(a, tol));  // a nan draw stays nan, as in Python
   double nf;
   fragmentation_limiters(nf, fv, vmin, nfmax, x_plus_y[i]);
   frag_volume[i] = fv;
@@ -671,7 +671,7 @@ k_feingold1988_fragmentation(double *__restrict__ n_fragment, double scale,
   const int64_t i = TID();
   if (i >= n) return;
   const double a = 1 - rand[i] * scale / x_plus_y[i];
-  double fv = -scale * sdm_log(a > fragtol ? a : fragtol), nf;
+  double fv = -scale * sdm_log(PYMAX(a, fragtol)), nf;  // a nan draw stays nan, as in Python
   fragmentation_limiters(nf, fv, vmin, nfmax, x_plus_y[i]);
   frag_volume[i] = fv;
   n_fragment[i] = nf;

@@ -329,7 +329,7 @@ __device__ __forceinline__ void breakup_params(const sdm_step_cfg &cfg, const Fu
       case SDM_FRAG_ALWAYS_N: fm = (mj + mk) / cfg.frag_param[0]; break;
       case SDM_FRAG_EXPONENTIAL: {
         const double a = 1 - u_b;
-        double fv = -cfg.frag_param[0] * sdm_log(a > 1e-5 ? a : 1e-5), nf;
+        double fv = -cfg.frag_param[0] * sdm_log(PYMAX(a, 1e-5)), nf;
         fragmentation_limiters(nf, fv, cfg.frag_vmin, cfg.frag_nfmax, vj + vk);
         fm = cfg.rho_w * fv;
         break;
@@ -343,7 +343,7 @@ __device__ __forceinline__ void breakup_params(const sdm_step_cfg &cfg, const Fu
       }
       case SDM_FRAG_FEINGOLD1988: {  // :487-499, physics/fragmentation_function/feingold1988.py
         const double a = 1 - u_b * cfg.frag_param[0] / (vj + vk);
-        double fv = -cfg.frag_param[0] * sdm_log(a > cfg.frag_param[1] ? a : cfg.frag_param[1]), nf;
+        double fv = -cfg.frag_param[0] * sdm_log(PYMAX(a, cfg.frag_param[1])), nf;
         fragmentation_limiters(nf, fv, cfg.frag_vmin, cfg.frag_nfmax, vj + vk);
         fm = cfg.rho_w * fv;
         break;
