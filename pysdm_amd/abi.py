@@ -28,6 +28,8 @@ FREEZING_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "sdm_free
 DEPOSITION_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "sdm_deposition.h")
 # and the aqueous-chemistry path
 CHEMISTRY_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "sdm_chemistry.h")
+# and the seeding path
+SEEDING_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "sdm_seeding.h")
 # SDM_HIP_LIB: another build of the same library (tuning variants); still no fallback
 HIP_LIB_PATH = os.environ.get("SDM_HIP_LIB") or os.path.join(_HERE, "libsdm_hip.so")
 
@@ -300,6 +302,7 @@ _condensation_library = None
 _freezing_library = None
 _deposition_library = None
 _chemistry_library = None
+_seeding_library = None
 
 
 def hip_library():
@@ -344,6 +347,15 @@ def chemistry_library():
         _chemistry_library = Library(HIP_LIB_PATH, "the HIP kernels of pysdm_amd",
                                      header=CHEMISTRY_HEADER_PATH)
     return _chemistry_library
+
+
+def seeding_library():
+    """libsdm_hip.so bound to include/sdm_seeding.h (same file, same contexts)"""
+    global _seeding_library  # pylint: disable=global-statement
+    if _seeding_library is None:
+        _seeding_library = Library(HIP_LIB_PATH, "the HIP kernels of pysdm_amd",
+                                   header=SEEDING_HEADER_PATH)
+    return _seeding_library
 
 
 def pcg64_state_inc(seed):

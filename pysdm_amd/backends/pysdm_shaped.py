@@ -20,6 +20,7 @@ from ..abi import pcg64_state_inc
 from .. import chemistry as chem
 from .. import deposition as dep
 from .. import freezing as frz
+from .. import seeding as seed
 from ..condensation import check_formulae, condensation_call, constants_of
 from ..displacement import SCHEMES
 from ..formulae import Formulae
@@ -642,6 +643,27 @@ def backend_class_for(engine_getter, name, doc=None):  # pylint: disable=too-man
                 [k0.data, k1.data, k2.data, k3.data], eq, float(timestep), droplet_volume.data,
                 pH.data, dissociation_factor_SO2.data, moles_O3.data, moles_H2O2.data,
                 moles_S_IV.data, moles_S_VI.data, self._chem_consts())
+
+        # ---- seeding (seeding_methods.py; include/sdm_seeding.h) ---------------------------------
+        def seeding(self, *, idx, multiplicity, extensive_attributes, seeded_particle_index,
+                    seeded_particle_multiplicity, seeded_particle_extensive_attributes,
+                    number_of_super_particles_to_inject):
+            """the first free slots (multiplicity 0) in slot order receive the seeds the seed
+            index names; cell id and position of a slot stay.  All columns raw (`.data`), as in
+            the reference.  With fewer free slots than asked for nothing is stored and ValueError
+            is raised (the reference asserts after having written)"""
+            number = int(number_of_super_particles_to_inject)
+            if number <= 0:
+                return
+            eng = self.engine
+            rows = extensive_attributes.data
+            status = eng.zeros(seed.STATUS_WORDS, np.int64)
+            eng.seeding_call(
+                "sdm_seeding", idx.data, multiplicity.data, rows, int(rows.shape[0]),
+                int(multiplicity.data.shape[0]), seeded_particle_index.data,
+                seeded_particle_multiplicity.data, seeded_particle_extensive_attributes.data,
+                int(seeded_particle_multiplicity.data.shape[0]), number, status)
+            seed.raise_if_refused(np.asarray(eng.download(status)), number)
 
         # ---- ambient thermodynamics (physics_methods.py) ----------------------------------------
         def _ambient_consts(self):

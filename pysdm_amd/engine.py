@@ -29,6 +29,8 @@ class Engine:
     deposition_library = None
     # likewise include/sdm_chemistry.h
     chemistry_library = None
+    # likewise include/sdm_seeding.h
+    seeding_library = None
 
     # ---- arrays -----------------------------------------------------------------------------
     def empty(self, shape, dtype):
@@ -97,6 +99,13 @@ class Engine:
         self._before_call()
         self.chemistry_library.invoke(symbol, self.handle, args)
 
+    def seeding_call(self, symbol, *args):
+        """a symbol of include/sdm_seeding.h"""
+        if self.seeding_library is None:
+            raise NotImplementedError(f"engine `{self.name}` has no seeding library")
+        self._before_call()
+        self.seeding_library.invoke(symbol, self.handle, args)
+
     def _before_call(self):
         pass
 
@@ -125,6 +134,7 @@ class HipEngine(Engine):
         self.freezing_library = abi.freezing_library()
         self.deposition_library = abi.deposition_library()
         self.chemistry_library = abi.chemistry_library()
+        self.seeding_library = abi.seeding_library()
         self.handle = abi.c_ptr()
         self.library.check(self.library.cdll.sdm_ctx_create(ctypes.byref(self.handle),
                                                             abi.c_int(device_index)))

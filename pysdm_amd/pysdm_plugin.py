@@ -21,6 +21,10 @@
    parameters (`setup_from_pysdm`); counters (`collision_rate`, ...) stay attributes of the
    returned object, as PySDM's products expect.
 
+3. Seeding.  `fuse(Seeding(...))` likewise: every injecting time step is ONE `sdm_seeding_step`
+   (shuffle of the seed index, injection, identity index, compaction) on PySDM's own arrays; the
+   position in the random stream is the one PySDM's `Random` of the wrapped dynamic holds.
+
 PySDM itself is imported lazily: this module loads (and fails loudly) only where PySDM exists.
 PySDM's ParticleAttributes keeps the permutation index, `cell_start`, the sorted flag and the
 number of valid super-droplets as name-mangled members (PySDM/impl/particle_attributes.py:13-46);
@@ -28,9 +32,11 @@ that is how PySDM's `Particulator` itself reaches them (particulator.py:301-313)
 fused step hands the state back.
 """
 import copy
+import ctypes
 import importlib
 
 from . import recipe as R
+from . import seeding as seed
 from .collisions import CollisionRunner
 from .population import Population
 
@@ -232,6 +238,79 @@ class FusedCollision(Collision):
         self._state.after()
 
 
+class Seeding:  # pylint: disable=too-few-public-methods
+    """root class: the fused dynamic takes PySDM's "Seeding" slot (see `Collision`)"""
+
+
+class FusedSeeding(Seeding):
+    """PySDM's `Seeding` dynamic (dynamics/seeding.py) with `Particulator.seeding`
+    (particulator.py:447-499) as one `sdm_seeding_step` per injecting time step.  As in PySDM a
+    seed is not placed in space: the slot keeps its cell id and position."""
+
+    def __init__(self, dynamic):
+        self.inner = dynamic
+        self.particulator = None
+
+    def register(self, builder):
+        self.particulator = builder.particulator
+        self.inner.register(builder)
+
+    def instantiate(self, *, builder):
+        own = copy.copy(self)
+        own.inner = copy.copy(self.inner)
+        own.register(builder)
+        return own
+
+    def __getattr__(self, name):
+        if name.startswith("__") or "inner" not in self.__dict__:
+            raise AttributeError(name)
+        return getattr(self.__dict__["inner"], name)
+
+    def __call__(self):
+        part, inner = self.particulator, self.inner
+        if part.n_steps == 0:
+            inner.post_register_setup_when_attributes_are_known()
+        number = inner.super_droplet_injection_rate(part.n_steps * part.dt)
+        if not number > 0:  # seeding.py:77: no shuffle, no random number
+            return
+        number = int(number)
+        n_seeds = len(inner.seeded_particle_multiplicity)
+        assert number <= n_seeds
+        attrs = part.attributes
+        seed.check_counts(part.n_sd, attrs.super_droplet_count, n_seeds, number)
+        idx = getattr(attrs, _PRIVATE + "idx")
+        rows = attrs.get_extensive_attribute_storage().data
+        rnd = inner.rnd  # this package's Random: the stream and the position in it
+        new_length = ctypes.c_int64(-1)
+        try:
+            part.backend.engine.seeding_call(
+                "sdm_seeding_step", idx.data, attrs["multiplicity"].data, rows,
+                int(rows.shape[0]), int(part.n_sd), inner.index.data,
+                inner.seeded_particle_multiplicity.data,
+                inner.seeded_particle_extensive_attributes.data, n_seeds, number,
+                int(rnd is not None), rnd.state_inc if rnd is not None else (0, 0, 0, 0),
+                rnd.offset if rnd is not None else 0, new_length)
+        except RuntimeError as error:
+            # refused on the device (the count check above makes that a matter of broken
+            # bookkeeping): the index was shuffled, so the numbers are spent, as on PySDM's own route
+            if rnd is not None and seed.shuffled_before_failing(error):
+                rnd.offset += n_seeds
+            raise
+        if rnd is not None:
+            rnd.offset += n_seeds
+        # what reset_idx() and sanitize() leave behind (particle_attributes.py:67-73,122-125)
+        live = int(new_length.value)
+        setattr(attrs, _PRIVATE + "valid_n_sd", live)
+        idx.length = idx.INT(live)
+        attrs.healthy = True
+        setattr(attrs, _PRIVATE + "sorted", False)
+        attrs.mark_updated("multiplicity")
+        for key in attrs.get_extensive_attribute_keys():
+            attrs.mark_updated(key)
+
+
 def fuse(dynamic):
-    """`dynamic`: a PySDM Collision / Coalescence / Breakup instance"""
+    """`dynamic`: a PySDM Collision / Coalescence / Breakup instance, or a PySDM Seeding"""
+    if type(dynamic).__name__ == "Seeding":
+        return FusedSeeding(dynamic)
     return FusedCollision(dynamic)

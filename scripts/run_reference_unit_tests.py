@@ -41,6 +41,10 @@ EXTRA = [  # the rows SURVEY 8(f) widened into: moments, displacement, storage o
     "backends/storage/test_setitem.py",
     "backends/test_ctor_defaults.py",
 ]
+# --seeding: the reference's cases of the injection logic alone, against the class bound to the
+# checker of include/sdm_seeding.h (the oracle does not implement that header); no part of the two
+# lists above
+SEEDING = ["backends/test_seeding_methods.py"]
 
 # test-id pattern -> why it does not pass (judged by hand from each failure)
 REASONS = [
@@ -70,6 +74,8 @@ def main():
     parser = argparse.ArgumentParser()
     parser.add_argument("--report", default=None)
     parser.add_argument("--extra", action="store_true", help="also the f-1 / f-3 / storage files")
+    parser.add_argument("--seeding", action="store_true",
+                        help="only backends/test_seeding_methods.py, on the seeding checker's class")
     args, extra_args = parser.parse_known_args()  # (what is not ours goes to pytest: -k, --tb)
     args.pytest_args = extra_args
     if not os.path.isdir(UNIT):
@@ -89,7 +95,22 @@ def main():
     plugin = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(plugin)
 
-    targets = [os.path.join(UNIT, f) for f in FILES + (EXTRA if args.extra else [])]
+    files = FILES + (EXTRA if args.extra else [])
+    under_test = "as_pysdm_backend(OracleBackend)"
+    if args.seeding:
+        from pysdm_amd.pysdm_plugin import as_pysdm_backend  # pylint: disable=import-outside-toplevel
+
+        # this repository's `tests` package for one import, then out of the way again: under that
+        # name the reference's test files must find the reference's own helpers
+        sys.path.insert(0, ROOT)
+        from tests.seeding_checker import SeedingCheckerBackend  # pylint: disable=import-outside-toplevel
+        sys.path.remove(ROOT)
+        for name in [m for m in sys.modules if m == "tests" or m.startswith("tests.")]:
+            del sys.modules[name]
+        files, under_test = SEEDING, "as_pysdm_backend(SeedingCheckerBackend)"
+        backends = importlib.import_module("PySDM.backends")
+        backends.CPU = backends.Numba = backends.HIP = as_pysdm_backend(SeedingCheckerBackend)
+    targets = [os.path.join(UNIT, f) for f in files]
     targets = [t for t in targets if os.path.exists(t)]
     code = pytest.main(targets + ["-p", "no:cacheprovider", "-q", "--rootdir", REFERENCE,
                                   "-W", "ignore", "-o", "addopts="] + args.pytest_args,
@@ -107,9 +128,9 @@ def main():
     summary = ", ".join(f"{v} {k}" for k, v in sorted(counts.items()))
     header = [
         "The reference's own unit tests against this package's backend class",
-        "(scripts/run_reference_unit_tests.py; class under test: as_pysdm_backend(OracleBackend), the",
+        f"(scripts/run_reference_unit_tests.py; class under test: {under_test}, the",
         "PySDM-shaped class HIP is, over the CPU checker's implementation of include/sdm_hip.h)",
-        f"files: {', '.join(FILES + (EXTRA if args.extra else []))}",
+        f"files: {', '.join(files)}",
         f"result: {summary}; {len(plugin.DESELECTED)} cases parametrised with the reference's own GPU "
         "class deselected",
         f"pytest exit code {int(code)}",
