@@ -397,6 +397,9 @@ int sdm_reduce_f64(sdm_ctx *ctx, int kind, const double *a, int64_t n, double *r
 #define SDM_FRAG_LOWLIST1982 7  /* lowlist82.py (straub_consts supplies CM, PI, Vedder's A, b) */
 #define SDM_EC_LOWLIST1982 3    /* coalescence_efficiencies/lowlist1982.py */
 
+#define SDM_VELOCITY_TERMINAL 0
+#define SDM_VELOCITY_MOMENTUM 1
+
 typedef struct sdm_step_cfg {
   int64_t n_sd, n_cell, n_attr;
   double dt, dv;
@@ -424,6 +427,14 @@ typedef struct sdm_step_cfg {
   uint64_t rng_state_inc[4];  /* PCG64 state/inc of seed (numpy.random.PCG64(seed).state) */
   int64_t gk_table_len;       /* Gunn-Kinzer table length (0 if unused) */
   double gk_factor;
+  /* where "relative fall velocity" comes from.  SDM_VELOCITY_TERMINAL (0): the Gunn-Kinzer table
+   * at the radius.  SDM_VELOCITY_MOMENTUM: attributes[momentum_attr][id] / |mass|, the reference's
+   * attribute once `RelaxedVelocity` is among the dynamics
+   * (attributes/physics/relative_fall_velocity.py); the table is not needed then, momentum_attr
+   * is a row other than mass_attr, and sharded runs are refused (SDM_E_ARG).  The row is updated
+   * like every extensive attribute.                                                          */
+  int32_t velocity_source;
+  int32_t momentum_attr;
 } sdm_step_cfg;
 
 /* ---- sharding of a multi-cell domain over several processes (one per GPU) -------------------

@@ -20,6 +20,7 @@ import numpy as np
 from . import abi
 from .engine import FLOAT, INT
 from .physics import constants as const
+from .population import MOMENTUM_ROW, VELOCITY_SOURCES
 from .terminal_velocity import LAWS
 
 READ_BACK, FRESH_CTL, MIRROR_VALID = 1, 2, 4
@@ -30,11 +31,23 @@ _DEVICE_ERRORS = {1: "a cell is larger than the per-cell kernel's capacity",
 
 class CollisionRunner:  # pylint: disable=too-many-instance-attributes
     def __init__(self, population, setup, *, dt, dv, route="fused",
-                 terminal_velocity="GunnKinzer1949", constants=None, read_back=True):
+                 terminal_velocity="GunnKinzer1949", constants=None, read_back=True,
+                 velocity="terminal"):
         if population.n_sd < 2:
             raise ValueError("No one to collide with!")
         if route not in ("fused", "chain"):
             raise ValueError(route)
+        if velocity not in VELOCITY_SOURCES:
+            raise ValueError(f"velocity={velocity!r}: one of {VELOCITY_SOURCES}")
+        if velocity != population.velocity_source:
+            raise ValueError(f"velocity={velocity!r}, but the population's velocity source is "
+                             f"{population.velocity_source!r}")
+        if (velocity == "momentum" and route == "fused"
+                and not population.engine.fused_momentum_velocity):
+            # such a fused step derives the fall velocity from the radius: it would run, and differ
+            raise NotImplementedError(
+                f"the fused collision step of engine `{population.engine.name}` cannot take the "
+                "fall velocity from the relative fall momentum; use route='chain'")
         if population.n_cell > 1 and setup.croupier == "global" and setup.adaptive:
             # the one configuration in which this package does NOT reproduce the reference, by
             # design ("Several cells, global croupier, adaptive")
@@ -49,6 +62,7 @@ class CollisionRunner:  # pylint: disable=too-many-instance-attributes
         self.setup = setup
         self.dt, self.dv = float(dt), float(dv)
         self.route = route
+        self.velocity = velocity
         self.read_back = read_back
         self.constants = constants or const.namespace()
         self.dt_range = setup.clamped_dt_range(self.dt)
@@ -112,7 +126,10 @@ class CollisionRunner:  # pylint: disable=too-many-instance-attributes
         cfg.kernel_berry_unit = desc.get("kernel_berry_unit", 1.0)
         cfg.max_multiplicity = int(setup.max_multiplicity)
         cfg.rng_state_inc = (abi.c_u64 * 4)(*abi.pcg64_state_inc(setup.seed))
-        if desc["needs_gk"]:
+        if self.velocity == "momentum":  # the velocity is a row of the block: no table
+            cfg.velocity_source = abi.VELOCITY_MOMENTUM
+            cfg.momentum_attr = pop.rows[MOMENTUM_ROW]
+        elif desc["needs_gk"]:
             if self._law_name != "GunnKinzer1949":
                 raise NotImplementedError("the fused step evaluates fall velocities from the "
                                           "Gunn-Kinzer table; use route='chain' for other laws")
@@ -143,7 +160,7 @@ class CollisionRunner:  # pylint: disable=too-many-instance-attributes
                     ("breakup_rate_deficit", self.breakup_rate_deficit),
                     ("ctl", pop.ctl), ("nm", pop.mirror)):
                 setattr(state, name, address(array))
-            if self.descriptor["needs_gk"]:
+            if self.descriptor["needs_gk"] and self.velocity != "momentum":
                 state.gk_a, state.gk_b = address(self.law.a), address(self.law.b)
             state.known_valid = -1
             if self.shard is not None:

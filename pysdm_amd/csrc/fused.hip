@@ -213,10 +213,17 @@ __device__ __forceinline__ double norm_factor_of(const sdm_step_cfg &cfg,
                           (double)(sd_num / 2);
 }
 
-__device__ __forceinline__ void derive_ru(const sdm_step_cfg &cfg, const FusedArgs &A, SD &v) {
+// `id`: the super-droplet `v` is the state of.  With SDM_VELOCITY_MOMENTUM the velocity is the
+// reference's `ratio(relative fall momentum, water mass)`, read from the SoA row as it is now (a
+// branch uniform over the launch); the radius comes from the mass either way
+__device__ __forceinline__ void derive_ru(const sdm_step_cfg &cfg, const FusedArgs &A, SD &v,
+                                          int64_t id) {
   const double inv = 1 / (3.14159265358979323846 * 4 / 3);
   v.r = radius_of_volume(volume_of_mass(v.m, cfg.rho_w), inv);
-  v.u = A.gk_a ? gk_interpolate(v.r, cfg.gk_factor, A.gk_a, A.gk_b, cfg.gk_table_len) : 0.0;
+  if (cfg.velocity_source == SDM_VELOCITY_MOMENTUM)
+    v.u = (A.attributes + (int64_t)cfg.momentum_attr * cfg.n_sd)[id] / fabs(v.m);
+  else
+    v.u = A.gk_a ? gk_interpolate(v.r, cfg.gk_factor, A.gk_a, A.gk_b, cfg.gk_table_len) : 0.0;
 }
 
 // state of super-droplet `id`: from the mirror if there is one, else from the SoA columns
@@ -235,7 +242,7 @@ __device__ __forceinline__ SD sd_load(const sdm_step_cfg &cfg, const FusedArgs &
       v.m = (A.attributes + (int64_t)cfg.mass_attr * cfg.n_sd)[id];
     }
     v.r = v.u = 0.0;
-    if (need_ru) derive_ru(cfg, A, v);
+    if (need_ru) derive_ru(cfg, A, v, id);
   }
   return v;
 }
@@ -248,7 +255,7 @@ __device__ __forceinline__ void sd_refresh(const sdm_step_cfg &cfg, const FusedA
   v.n = A.multiplicity[id];
   v.m = (A.attributes + (int64_t)cfg.mass_attr * cfg.n_sd)[id];
   if (A.nm_wide) {
-    derive_ru(cfg, A, v);
+    derive_ru(cfg, A, v, id);
     ((double4 *)A.nm)[id] = make_double4(__longlong_as_double(v.n), v.m, v.r, v.u);
   } else {
     ((double2 *)A.nm)[id] = make_double2(__longlong_as_double(v.n), v.m);
@@ -658,7 +665,7 @@ __device__ __forceinline__ int coalesce_known(const sdm_step_cfg &cfg, const Fus
     sk.m += g * sj.m;
     A.multiplicity[j] = sj.n;
     mass[k] = sk.m;
-    if (A.nm_wide) derive_ru(cfg, A, sk);
+    if (A.nm_wide) derive_ru(cfg, A, sk, k);  // (one attribute: never the momentum source)
   } else {
     const int64_t half = sk.n / 2;
     sj.n = half;
@@ -670,7 +677,7 @@ __device__ __forceinline__ int coalesce_known(const sdm_step_cfg &cfg, const Fus
     mass[j] = v;
     mass[k] = v;
     if (A.nm_wide) {
-      derive_ru(cfg, A, sk);
+      derive_ru(cfg, A, sk, k);
       sj.r = sk.r;
       sj.u = sk.u;
     }
@@ -2400,7 +2407,15 @@ static int collision_step(sdm_ctx *ctx, const sdm_step_cfg *cfg, sdm_step_state 
           st->stats_n_substep && st->collision_rate && st->collision_rate_deficit &&
           st->coalescence_rate && st->ctl);
   ARG_TRY(!cfg->enable_breakup || (st->breakup_rate && st->breakup_rate_deficit));
-  ARG_TRY((cfg->kernel != SDM_KERNEL_GEOMETRIC && cfg->kernel != SDM_KERNEL_PARAMETERIZED) ||
+  ARG_TRY(cfg->velocity_source == SDM_VELOCITY_TERMINAL ||
+          cfg->velocity_source == SDM_VELOCITY_MOMENTUM);
+  const bool from_momentum = cfg->velocity_source == SDM_VELOCITY_MOMENTUM;
+  // (the momentum is a row of its own, so the routes for one extensive attribute are never taken)
+  ARG_TRY(!from_momentum || (cfg->momentum_attr >= 0 && cfg->momentum_attr < cfg->n_attr &&
+                             cfg->momentum_attr != cfg->mass_attr));
+  ARG_TRY(!from_momentum || (!st->cell_owned && !st->exchange && st->shard_world <= 1));
+  ARG_TRY(from_momentum ||
+          (cfg->kernel != SDM_KERNEL_GEOMETRIC && cfg->kernel != SDM_KERNEL_PARAMETERIZED) ||
           (st->gk_a && st->gk_b && cfg->gk_table_len > 0));
   ARG_TRY(cfg->kernel >= SDM_KERNEL_GOLOVIN && cfg->kernel <= SDM_KERNEL_LINEAR);
   ARG_TRY(cfg->adaptive || cfg->substeps >= 1);

@@ -31,6 +31,11 @@ class Engine:
     chemistry_library = None
     # likewise include/sdm_seeding.h
     seeding_library = None
+    # likewise include/sdm_relaxed_velocity.h
+    relaxed_velocity_library = None
+    # whether the fused collision step of `library` can take the fall velocity from the
+    # "relative fall momentum" row; an engine that cannot must refuse, not ignore the request
+    fused_momentum_velocity = False
 
     # ---- arrays -----------------------------------------------------------------------------
     def empty(self, shape, dtype):
@@ -106,6 +111,13 @@ class Engine:
         self._before_call()
         self.seeding_library.invoke(symbol, self.handle, args)
 
+    def relaxed_velocity_call(self, symbol, *args):
+        """a symbol of include/sdm_relaxed_velocity.h"""
+        if self.relaxed_velocity_library is None:
+            raise NotImplementedError(f"engine `{self.name}` has no relaxed-velocity library")
+        self._before_call()
+        self.relaxed_velocity_library.invoke(symbol, self.handle, args)
+
     def _before_call(self):
         pass
 
@@ -123,6 +135,8 @@ class HipEngine(Engine):
     """one sdm_ctx per process and device; follows torch's current stream"""
 
     name = "hip"
+    # fused.hip reads the velocity from the momentum row (sdm_step_cfg.velocity_source)
+    fused_momentum_velocity = True
     _instances = {}
 
     def __init__(self, device_index):
@@ -135,6 +149,7 @@ class HipEngine(Engine):
         self.deposition_library = abi.deposition_library()
         self.chemistry_library = abi.chemistry_library()
         self.seeding_library = abi.seeding_library()
+        self.relaxed_velocity_library = abi.relaxed_velocity_library()
         self.handle = abi.c_ptr()
         self.library.check(self.library.cdll.sdm_ctx_create(ctypes.byref(self.handle),
                                                             abi.c_int(device_index)))

@@ -28,6 +28,8 @@ from .engine import FLOAT, INT
 from .physics import constants as const
 
 MASS_ROW = "signed water mass"
+MOMENTUM_ROW = "relative fall momentum"
+VELOCITY_SOURCES = ("terminal", "momentum")
 
 
 def to_integer_multiplicities(values):
@@ -71,9 +73,10 @@ def locate(positions, grid):
 class Population:  # pylint: disable=too-many-instance-attributes
     def __init__(self, engine, *, multiplicity, mass=None, volume=None, cell_id=None, n_cell=1,
                  more_extensive=None, grid=None, cell_origin=None, position_in_cell=None,
-                 rho_w=const.rho_w):
+                 rho_w=const.rho_w, velocity_source="terminal"):
         if (mass is None) == (volume is None):
             raise ValueError("give either `mass` or `volume`")
+        self._set_velocity_source(velocity_source, more_extensive or {})
         self.engine = engine
         self.rho_w = rho_w
         multiplicity = to_integer_multiplicities(multiplicity)
@@ -128,11 +131,13 @@ class Population:  # pylint: disable=too-many-instance-attributes
 
     @classmethod
     def adopt(cls, engine, *, perm, perm_spare, multiplicity, extensive, rows, cell_id,
-              cell_order, cell_start, live, ordered, healthy=None, rho_w=const.rho_w):
+              cell_order, cell_start, live, ordered, healthy=None, rho_w=const.rho_w,
+              velocity_source="terminal"):
         """a Population over columns that already live in the engine's memory and belong to
         someone else (e.g. PySDM's ParticleAttributes, see pysdm_amd.pysdm_plugin); nothing is
         copied"""
         self = cls.__new__(cls)
+        self._set_velocity_source(velocity_source, rows)
         self.engine, self.rho_w = engine, rho_w
         self.n_sd = int(multiplicity.shape[0])
         self.n_cell = int(cell_order.shape[0])
@@ -159,6 +164,21 @@ class Population:  # pylint: disable=too-many-instance-attributes
     @property
     def mass(self):
         return self.extensive[self.rows[MASS_ROW]]
+
+    @property
+    def momentum(self):
+        """the "relative fall momentum" row (PySDM/attributes/physics/relative_fall_velocity.py)"""
+        return self.extensive[self.rows[MOMENTUM_ROW]]
+
+    def _set_velocity_source(self, source, rows):
+        """where "relative fall velocity" comes from: the terminal velocity of the radius, or -
+        as in the reference once `RelaxedVelocity` is among the dynamics - momentum / water mass"""
+        if source not in VELOCITY_SOURCES:
+            raise ValueError(f"velocity_source={source!r}: one of {VELOCITY_SOURCES}")
+        if source == "momentum" and MOMENTUM_ROW not in rows:
+            raise ValueError(f"velocity_source='momentum' needs the extensive row "
+                             f"{MOMENTUM_ROW!r} (more_extensive=...)")
+        self.velocity_source = source
 
     def touch_state(self):
         """multiplicities / extensive attributes changed"""
@@ -244,8 +264,30 @@ class Population:  # pylint: disable=too-many-instance-attributes
                              self.n_sd)
         return self._cached("area", build)
 
+    def derived_buffer(self, name):
+        """the array behind the cached column `name`, for a kernel that computes the column
+        together with the state it belongs to (then: touch_state(), publish_derived(name))"""
+        entry = self._derived.get(name)
+        if entry is None:
+            entry = self._derived[name] = (None, self.engine.empty(self.n_sd, FLOAT))
+        return entry[1]
+
+    def publish_derived(self, name):
+        """the buffer of `derived_buffer(name)` holds the column of the current state"""
+        self._derived[name] = (self.state_version, self._derived[name][1])
+
+    def water_mass(self):
+        """|signed water mass| (attributes/physics/water_mass.py: AbsWaterMass)"""
+        return self._cached("water mass", lambda out: self.engine.call(
+            "sdm_elementwise_f64", 8, out, self.mass, None, 0.0, self.n_sd))
+
     def fall_velocity(self, law):
-        """terminal velocity of every slot by `law` (a pysdm_amd.terminal_velocity object)"""
+        """"relative fall velocity" of every slot: the terminal velocity by `law` (a
+        pysdm_amd.terminal_velocity object), or momentum / water mass if that is the population's
+        velocity source (`law` is not looked at then)"""
+        if self.velocity_source == "momentum":
+            return self._cached("fall velocity", lambda out: self.engine.call(
+                "sdm_elementwise_f64", 3, out, self.momentum, self.water_mass(), 0.0, self.n_sd))
         return self._cached("fall velocity", lambda out: law.evaluate(self.engine, out,
                                                                       self.radius(), self.n_sd))
 

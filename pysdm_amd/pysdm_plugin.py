@@ -25,6 +25,12 @@
    (shuffle of the seed index, injection, identity index, compaction) on PySDM's own arrays; the
    position in the random stream is the one PySDM's `Random` of the wrapped dynamic holds.
 
+4. Relaxed fall velocity.  `fuse(RelaxedVelocity(...))` likewise: every call is ONE
+   `sdm_relaxed_velocity_step` on PySDM's own "signed water mass" and "relative fall momentum"
+   rows.  With `RelaxedVelocity` among the dynamics PySDM's "relative fall velocity" is momentum /
+   water mass; the fused collision step derives it from the radius, so `fuse(<collision
+   dynamic>)` refuses to run beside it (PySDM's own dynamic on the plugged backend does run).
+
 PySDM itself is imported lazily: this module loads (and fails loudly) only where PySDM exists.
 PySDM's ParticleAttributes keeps the permutation index, `cell_start`, the sorted flag and the
 number of valid super-droplets as name-mangled members (PySDM/impl/particle_attributes.py:13-46);
@@ -35,7 +41,9 @@ import copy
 import ctypes
 import importlib
 
+from . import abi
 from . import recipe as R
+from . import relaxed_velocity as relax
 from . import seeding as seed
 from .collisions import CollisionRunner
 from .population import Population
@@ -128,7 +136,7 @@ class _AdoptedState:
     """PySDM's ParticleAttributes seen as a Population (arrays shared, bookkeeping copied in
     before and back after every fused call)"""
 
-    def __init__(self, particulator):
+    def __init__(self, particulator, velocity_source="terminal"):
         self.attributes = attrs = particulator.attributes
         self.idx = getattr(attrs, _PRIVATE + "idx")
         self.caretaker = getattr(attrs, _PRIVATE + "cell_caretaker")
@@ -140,7 +148,7 @@ class _AdoptedState:
             rows={name: row for row, name in enumerate(keys)}, cell_id=attrs["cell id"].data,
             cell_order=attrs.cell_idx.data, cell_start=getattr(attrs, _PRIVATE + "cell_start").data,
             live=getattr(attrs, _PRIVATE + "valid_n_sd"), ordered=getattr(attrs, _PRIVATE + "sorted"),
-            rho_w=particulator.formulae.constants.rho_w)
+            rho_w=particulator.formulae.constants.rho_w, velocity_source=velocity_source)
         self.stamps = None
 
     def _stamps(self):
@@ -228,11 +236,21 @@ class FusedCollision(Collision):
             return
         part = self.particulator
         if self.runner is None:
-            self._state = _AdoptedState(part)
+            # with RelaxedVelocity among the dynamics "relative fall velocity" is momentum / water
+            # mass (relative_fall_velocity.py:14,27): the step reads it from the extensive row
+            relaxed = "RelaxedVelocity" in getattr(part, "dynamics", ())
+            if relaxed and not part.backend.engine.fused_momentum_velocity:
+                # a fused step that derives the velocity from the radius would run and differ
+                raise NotImplementedError(
+                    "fuse(<collision dynamic>) beside RelaxedVelocity: the fused collision step "
+                    f"of engine `{part.backend.engine.name}` cannot take the fall velocity from "
+                    "the relative fall momentum; register PySDM's own dynamic instead")
+            velocity = "momentum" if relaxed else "terminal"
+            self._state = _AdoptedState(part, velocity_source=velocity)
             setup = setup_from_pysdm(self.inner, part.formulae)
             self.runner = CollisionRunner(self._state.population, setup, dt=part.dt,
                                           dv=part.mesh.dv, route="fused",
-                                          constants=part.formulae.constants)
+                                          constants=part.formulae.constants, velocity=velocity)
         self._state.before()
         self.runner.run(1)
         self._state.after()
@@ -309,8 +327,107 @@ class FusedSeeding(Seeding):
             attrs.mark_updated(key)
 
 
+class RelaxedVelocity:  # pylint: disable=too-few-public-methods
+    """root class: the fused dynamic takes PySDM's "RelaxedVelocity" slot (see `Collision`),
+    which is what PySDM's attribute variants look for (relative_fall_velocity.py:14,27)"""
+
+
+class FusedRelaxedVelocity(RelaxedVelocity):
+    """PySDM's `RelaxedVelocity` dynamic (dynamics/relaxed_velocity.py) as one
+    `sdm_relaxed_velocity_step` per call on PySDM's own rows"""
+
+    _OWN = ("inner", "particulator", "_cfg", "_table", "_status")
+
+    def __init__(self, dynamic):
+        self.inner = dynamic
+        self.particulator = None
+        self._cfg = self._table = self._status = None
+
+    def __setattr__(self, name, value):
+        # options (c, constant) belong to the wrapped dynamic
+        if name in self._OWN or "inner" not in self.__dict__:
+            object.__setattr__(self, name, value)
+        else:
+            setattr(self.__dict__["inner"], name, value)
+            object.__setattr__(self, "_cfg", None)
+
+    def register(self, builder):
+        self.particulator = builder.particulator
+        formulae = builder.particulator.formulae
+        shape = getattr(formulae, "particle_shape_and_density", None)
+        shape_name = shape if isinstance(shape, str) else getattr(
+            shape, "__name__", type(shape).__name__)
+        if shape_name != "LiquidSpheres":
+            raise NotImplementedError(f"fuse(RelaxedVelocity): particle_shape_and_density="
+                                      f"{shape_name!r}; implemented for 'LiquidSpheres'")
+        if self._law_name() not in relax.LAW_CODES:
+            raise NotImplementedError(
+                f"fuse(RelaxedVelocity): terminal_velocity={self._law_name()!r} is not offered "
+                "fused; register PySDM's own dynamic (stage-by-stage route)")
+        self.inner.register(builder)
+
+    def instantiate(self, *, builder):
+        own = copy.copy(self)
+        own.inner = copy.copy(self.inner)
+        own.register(builder)
+        return own
+
+    def __getattr__(self, name):
+        # calculate_tau / calculate_scale_factor and the options are the wrapped dynamic's
+        if name.startswith("__") or "inner" not in self.__dict__:
+            raise AttributeError(name)
+        return getattr(self.__dict__["inner"], name)
+
+    def _law_name(self):
+        law = self.particulator.formulae.terminal_velocity
+        return law if isinstance(law, str) else getattr(law, "__name__", type(law).__name__)
+
+    def _config(self):
+        part, inner = self.particulator, self.inner
+        if self._cfg is None:
+            cfg = abi.RelaxedVelocityCfg()
+            cfg.n_sd, cfg.dt = int(part.n_sd), float(part.dt)
+            cfg.c, cfg.constant = float(inner.c), int(bool(inner.constant))
+            cfg.rho_w = part.formulae.constants.rho_w
+            cfg.law = relax.LAW_CODES[self._law_name()]
+            self._table = (None, None)
+            if cfg.law == 0:
+                table = inner.terminal_vel_attr.approximation
+                cfg.gk_table_len, cfg.gk_factor = len(table.a), float(table.factor)
+                cfg.gk_top = float(table.maximum_radius)
+                self._table = (table.a.data, table.b.data)
+            else:
+                k = part.formulae.constants
+                cfg.rogers_yau = (abi.c_f64 * 5)(
+                    k.ROGERS_YAU_TERM_VEL_SMALL_K, k.ROGERS_YAU_TERM_VEL_MEDIUM_K,
+                    k.ROGERS_YAU_TERM_VEL_LARGE_K, k.ROGERS_YAU_TERM_VEL_SMALL_R_LIMIT,
+                    k.ROGERS_YAU_TERM_VEL_MEDIUM_R_LIMIT)
+            self._cfg = cfg
+        return self._cfg
+
+    def __call__(self):
+        part, inner = self.particulator, self.inner
+        engine, attrs = part.backend.engine, part.attributes
+        keys = list(attrs.get_extensive_attribute_keys())
+        rows = attrs.get_extensive_attribute_storage().data
+        cfg = self._config()
+        if self._status is None:
+            self._status = engine.zeros(relax.STATUS_WORDS, int)
+        engine.relaxed_velocity_call(
+            "sdm_relaxed_velocity_step", cfg, rows[keys.index("signed water mass")],
+            rows[keys.index("relative fall momentum")], None, *self._table, self._status)
+        if cfg.law == 0 and int(engine.download(self._status)[relax.STATUS_ABOVE_TOP]) != 0:
+            # nothing was stored: PySDM's own error, raised by PySDM's own attribute
+            inner.terminal_vel_attr.get()
+            raise ValueError(f"Radii can be interpolated up to {cfg.gk_top} m")
+        attrs.mark_updated("relative fall momentum")
+
+
 def fuse(dynamic):
-    """`dynamic`: a PySDM Collision / Coalescence / Breakup instance, or a PySDM Seeding"""
+    """`dynamic`: a PySDM Collision / Coalescence / Breakup instance, a PySDM Seeding or a PySDM
+    RelaxedVelocity"""
     if type(dynamic).__name__ == "Seeding":
         return FusedSeeding(dynamic)
+    if type(dynamic).__name__ == "RelaxedVelocity":
+        return FusedRelaxedVelocity(dynamic)
     return FusedCollision(dynamic)

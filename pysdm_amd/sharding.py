@@ -258,6 +258,9 @@ def attach_replay(runner, rank, world, trace):
 def _sharded(runner):
     if runner.route != "fused":
         raise ValueError("sharding drives the fused route")
+    if runner.velocity == "momentum":
+        raise NotImplementedError("sharded runs with the fall velocity taken from the relative "
+                                  "fall momentum")
     runner.read_back = True
     runner.counts_global_pairs = True  # every process counts the pairs of all cells
     runner._state = None  # pylint: disable=protected-access
@@ -332,6 +335,9 @@ def attach_displacement(displacement, shard):
     collision runner's (`runner.shard`), or a Shard of its own for a run without collisions"""
     if displacement.route != "fused":
         raise ValueError("sharding drives the fused route")
+    if displacement.population.velocity_source == "momentum":
+        raise NotImplementedError("sharded runs with the fall velocity taken from the relative "
+                                  "fall momentum")
     displacement.shard = shard
     return displacement
 
