@@ -1,7 +1,9 @@
 """time line of one launch of k_pair_all_sort from a -DPAIR_PROFILE build: which workgroup (sort /
 pair) ran when and on which CU, and how many workgroups of the kernel the runtime keeps on a CU:
-SDM_HIP_LIB=build_variants/libsdm_pairprof.so PYTHONPATH=. python profiles/tools/pair_profile.py"""
+SDM_HIP_LIB=build_variants/libsdm_pairprof.so PYTHONPATH=. python profiles/tools/pair_profile.py
+Also, per event tile, the XCDs its two pair workgroups ran on (SDM_WALK_LOCAL=0: grid order)."""
 import ctypes
+import os
 import sys
 from collections import defaultdict
 
@@ -98,8 +100,38 @@ def describe(rows, verbose):
     return res
 
 
+def tile_xcds(rows):
+    """the XCDs of the pair workgroups of every event tile (two workgroups of 2048 positions per
+    4096-event tile), through the kernel's own block order where the library has one"""
+    n_pair = grid - n_tiles
+    logical = np.arange(n_pair)
+    if hasattr(lib, "sdm_debug_walk_block_map") and os.environ.get("SDM_WALK_LOCAL", "1") != "0":
+        buf = (ctypes.c_int * n_pair)()
+        assert lib.sdm_debug_walk_block_map(n_pair, 2, buf) == 0
+        logical = np.array(buf[:], dtype=np.int64)
+    xcc = (rows[:, 3] >> 32) & 0xF
+    block = np.arange(grid)
+    share = float(np.mean(xcc[8:] == xcc[:-8]))
+    print(f"workgroups b and b + 8 on the same XCD: {100 * share:.1f} % of {grid - 8}; "
+          f"b and b + 1: {100 * float(np.mean(xcc[1:] == xcc[:-1])):.1f} %")
+    print("XCD of workgroups 0..15:", xcc[:16].tolist(), " (b % 8 == XCD for "
+          f"{100 * float(np.mean(xcc == block % 8)):.1f} %, (b % 8 - XCD) % 8 constant: "
+          f"{len(set(((block - xcc) % 8).tolist())) == 1})")
+    per_tile = defaultdict(set)
+    for b in range(n_pair):
+        per_tile[int(logical[b]) // 2].add(int(xcc[n_tiles + b]))
+    counts = defaultdict(int)
+    for xs in per_tile.values():
+        counts[len(xs)] += 1
+    print("XCDs per tile's pair workgroups: number of tiles",
+          {k: counts[k] for k in sorted(counts)})
+    for t in sorted(per_tile)[:8]:
+        print(f"  tile {t}: XCDs {sorted(per_tile[t])}")
+
+
 print("--- launch 0 ---")
 describe(runs[0], True)
+tile_xcds(runs[0])
 print("--- medians over", len(runs), "launches ---")
 all_res = [describe(r, False) for r in runs]
 for k in all_res[0]:

@@ -88,6 +88,7 @@ struct sdm_ctx {
   int64_t opt_max_substeps;      // SDM_OPT_MAX_SUBSTEPS (0: none)
   int opt_cell_shape;            // SDM_OPT_CELL_SHAPE
   int opt_records, opt_no_presort, opt_no_cell_copy;  // SDM_OPT_REC_FORMAT / _NO_PRESORT / _NO_CELL_COPY
+  int opt_no_walk_local;         // SDM_OPT_WALK_LOCAL
   int64_t stats[SDM_N_STATS];    // SDM_STAT_* (host-side counters, sdm_ctx_read_stats)
   // fused.hip: what a multi-cell adaptive step knows at its end, for the next step of the same call
   // (valid length, an upper bound of the cell sizes; the state is sorted) - saves that step's
@@ -104,7 +105,7 @@ struct sdm_ctx {
     uint64_t off_before, off_b_before;  // stream positions to return to if it is discarded
     u128 s_rand, s_rand_b;
     const void *rec, *ovf_head, *ovf_next;
-    int rec_fmt;
+    int rec_fmt, walk_tile, walk_tiles;
     int64_t *cur, *alt;  // permutation buffers as its kernels left them (cur: written)
   } ahead;
   // displacement.hip (sharded step): precipitated masses by position, zero between uses
@@ -224,6 +225,20 @@ int sdm_reserve(sdm_ctx *ctx, size_t bytes);
 static inline unsigned grid_for(int64_t n, int per_block = SDM_BLOCK) {
   int64_t g = (n + per_block - 1) / per_block;
   return (unsigned)(g < 1 ? 1 : g);
+}
+
+// Logical block of physical workgroup `b` of a grid of `n_blocks` whose `G` consecutive logical
+// blocks share one event tile of the shuffle build (fused.hip: the pair kernels' walks).  Workgroups
+// are dealt round-robin over the 8 XCDs, whose L2s are private; the map gives the G workgroups of a
+// tile the physical numbers b, b + 8, .., b + 8 (G - 1), so that the tile's segment of successor
+// words is fetched into one L2 instead of up to eight.  Groups of 8 G blocks cover 8 tiles; a last,
+// incomplete group keeps the identity.  A bijection of [0, n_blocks) for every n_blocks and G >= 1;
+// where a workgroup really runs is the hardware's business - a speed hint, nothing relies on it.
+#define SDM_XCDS 8
+__host__ __device__ inline unsigned walk_block_map(unsigned b, unsigned n_blocks, unsigned G) {
+  const unsigned span = SDM_XCDS * G, first = b - b % span, r = b - first;
+  if (first + span > n_blocks) return b;
+  return first + (r % SDM_XCDS) * G + r / SDM_XCDS;
 }
 
 // carve helper for the scratch arena (256-B aligned pieces)

@@ -109,6 +109,9 @@ struct FusedArgs {
   const void *rec;  // records of layout rec_fmt (shuffle_device.h: SDM_REC_*)
   int rec_fmt;
   const int32_t *ovf_head, *ovf_next;
+  // successor words: events per tile of the build (shuffle_build.h) when the pair kernels take
+  // their workgroups tile by tile (pair_block), 0 = in grid order; tiles the tables are padded to
+  int walk_tile, walk_tiles;
   const int64_t *idx_prev;  // previous permutation (source of the dead tail)
   // {multiplicity, mass} of each super-droplet side by side (one random line per gather instead
   // of two); a mirror of the SoA columns kept current by the update code, NULL = not in use
@@ -183,24 +186,38 @@ __global__ void __launch_bounds__(SDM_CNT_SLOTS) k_fold_counters(FusedArgs A) {
 }
 
 // one draw per thread: element (block_first + tid) of the stream starting at `s_base`
-__device__ __forceinline__ double stream_draw(u128 s_base, u128 inc, const u128 *__restrict__ tab,
-                                              u128 *lds_slot, uint64_t add = 0,
+// (`block`: the workgroup's logical number, pair_block)
+__device__ __forceinline__ double stream_draw(unsigned block, u128 s_base, u128 inc,
+                                              const u128 *__restrict__ tab, u128 *lds_slot,
+                                              uint64_t add = 0,
                                               const u128 *__restrict__ aff = nullptr) {
   // ready affine maps (common.h: pcg_aff): block b starts b * SDM_BLOCK draws in =
   // (b / PER) strides + (b % PER) * SDM_BLOCK, so two multiply-adds per thread and no exchange
   // through LDS, instead of a bit-by-bit jump by thread 0 and another by every thread
   constexpr int PER = PCG_AFF_STRIDE / SDM_BLOCK;
-  if (aff && add == 0 && blockIdx.x / PER < PCG_AFF_TILES) {
-    u128 state = pcg_apply(pcg_apply(s_base, aff, PCG_AFF_SMALL + (int64_t)(blockIdx.x / PER)),
-                           aff, (int64_t)(blockIdx.x % PER) * SDM_BLOCK + threadIdx.x);
+  if (aff && add == 0 && block / PER < PCG_AFF_TILES) {
+    u128 state = pcg_apply(pcg_apply(s_base, aff, PCG_AFF_SMALL + (int64_t)(block / PER)),
+                           aff, (int64_t)(block % PER) * SDM_BLOCK + threadIdx.x);
     state = state * pcg_mult() + inc;
     return pcg_output(state);
   }
-  if (threadIdx.x == 0) *lds_slot = pcg_jump(s_base, tab, (uint64_t)blockIdx.x * SDM_BLOCK + add);
+  if (threadIdx.x == 0) *lds_slot = pcg_jump(s_base, tab, (uint64_t)block * SDM_BLOCK + add);
   __syncthreads();
   u128 state = pcg_jump(*lds_slot, tab, (uint64_t)threadIdx.x);
   state = state * pcg_mult() + inc;
   return pcg_output(state);
+}
+
+// Logical number of workgroup `b` of the `n_blocks` workgroups (`threads` each, two positions per
+// thread) of a pair kernel that walks successor words: tile by tile over the XCDs (common.h:
+// walk_block_map).  Pair slots, draws and workgroup 0's duties derive from it; the load-spreading
+// hashes (counter slots, pair lists, block_min) keep the physical number - any bijection will do.
+__device__ __forceinline__ unsigned pair_block(const FusedArgs &A, unsigned b, unsigned n_blocks,
+                                               int threads) {
+#ifdef WALK_NO_MAP  // (tuning builds: the grid order with everything else as it is)
+  return b;
+#endif
+  return A.walk_tile ? walk_block_map(b, n_blocks, (unsigned)(A.walk_tile / (2 * threads))) : b;
 }
 
 // collisions_methods.py:643-650 (left-to-right evaluation)
@@ -478,11 +495,19 @@ __device__ __forceinline__ double pair_prob_value(const sdm_step_cfg &cfg, const
   return prob;
 }
 
+// k_pair_all_sort: the words first[2d], first[2d + 1] of the slot, loaded ahead, and the segment of
+// ssucc in LDS that the walk's first look-up may be taken from (seg == NULL: none)
+struct WalkSeg {
+  const uint32_t *seg;
+  uint32_t seg_first, seg_len, n0, n1;
+};
+
 // pairing (find_pairs + sort_within_pair), kernel, probability, [Ec, fragment mass], [optimal dt]
 // for pair slot d; `u_b` = the slot's draw of the breakup streams
 template <int KERNEL, bool BREAKUP>
 __device__ __forceinline__ PairInfo pair_prob_body(const sdm_step_cfg &cfg, const FusedArgs &A,
-                                                   int64_t d, int64_t W, double u_b) {
+                                                   int64_t d, int64_t W, double u_b,
+                                                   const WalkSeg *L = nullptr) {
   PairInfo R;
   R.have = false; R.off = 2; R.j = R.k = R.nj = R.nk = R.cid_j = 0;
   R.prob = 0.0; R.dt_optimal = INFINITY;
@@ -492,7 +517,10 @@ __device__ __forceinline__ PairInfo pair_prob_body(const sdm_step_cfg &cfg, cons
   if (cfg.n_cell == 1) {
     if (2 * d + 1 < W) { R.have = true; i = 2 * d; }
     if (A.rec) {  // permutation resolved here (shuffle_local of the single cell [0, W))
-      if (R.have) {
+      if (R.have && L && L->seg) {
+        walk_chain2_seg((const uint32_t *)A.ovf_head, (const uint32_t *)A.ovf_next, L->seg,
+                        L->seg_first, L->seg_len, L->n0, L->n1, tj, tk);
+      } else if (R.have) {
         walk_ids2(A.rec, A.rec_fmt, A.ovf_head, A.ovf_next, (int32_t)(2 * d),
                   (int32_t)(2 * d + 1), 0, tj, tk);
       } else {
@@ -792,11 +820,12 @@ template <int KERNEL, bool BREAKUP>
 __global__ void __launch_bounds__(SDM_BLOCK) k_pair_all(sdm_step_cfg cfg, FusedArgs A) {
   __shared__ u128 lds[2];
   const int64_t W = A.ctl[CTL_WORK];
-  const int64_t d = TID();
+  const unsigned lb = pair_block(A, blockIdx.x, gridDim.x, SDM_BLOCK);
+  const int64_t d = (int64_t)lb * SDM_BLOCK + threadIdx.x;
   if (d == 0) A.ctl[CTL_PAIRS] += W / 2;  // lets a caller count pairs without reading back per step
-  const double u = stream_draw(A.s_rand, A.rng_inc, A.rng_tab, &lds[0],
+  const double u = stream_draw(lb, A.s_rand, A.rng_inc, A.rng_tab, &lds[0],
                                A.dev_off ? A.dev_off[0] + A.rand_extra : 0, A.rng_aff);
-  const double u_b = BREAKUP ? stream_draw(A.s_rand_b, A.rng_inc, A.rng_tab, &lds[1],
+  const double u_b = BREAKUP ? stream_draw(lb, A.s_rand_b, A.rng_inc, A.rng_tab, &lds[1],
                                            A.dev_off ? A.dev_off[1] : 0, A.rng_aff)
                              : 0.0;
   PairInfo R;
@@ -887,12 +916,39 @@ k_pair_all_sort(sdm_step_cfg cfg, FusedArgs A, SortAhead X) {
     return;
   }
   const int64_t W = A.ctl[CTL_WORK];
-  const int64_t d = (int64_t)(blockIdx.x - X.n_tiles) * BIN_THREADS + threadIdx.x;
+  // (two pair workgroups per tile: block numbers 8 apart, pair_block)
+  const unsigned lb = pair_block(A, blockIdx.x - X.n_tiles, gridDim.x - X.n_tiles, BIN_THREADS);
+  const int64_t d = (int64_t)lb * BIN_THREADS + threadIdx.x;
+  // The first look-up of a walk: for the 63 % of the positions whose own event is their last it
+  // is an S word whose place lies in the position's own tile (shuffle_build.h: place = tile_first +
+  // at) - 4096 random 4-byte reads per tile into one 16-KB segment of ssucc.  The workgroup loads
+  // its tile's segment coalesced (16 bytes per lane, in flight together with the slot's words of
+  // `first`) into the dynamic LDS that only the sorting workgroups used, and the walks take that
+  // look-up from there.  Successor words from 4096-event tiles only; the tables are whole tiles.
+  WalkSeg L;
+  L.seg = nullptr; L.seg_first = L.seg_len = L.n0 = L.n1 = 0;
+  const int64_t my_tile = 2 * (int64_t)lb * BIN_THREADS / EV_TILE;
+#ifdef WALK_NO_SEG  // (tuning builds: every look-up from the tables)
+  if (false) {
+#else
+  if (A.walk_tile == EV_TILE && A.rec_fmt == SDM_REC_CHAIN && my_tile < A.walk_tiles) {  // uniform
+#endif
+    const uint2 w = *(const uint2 *)((const uint32_t *)A.rec + 2 * d);
+    const sort_v4u *from = (const sort_v4u *)((const uint32_t *)A.ovf_next + my_tile * EV_TILE);
+    for (int q = threadIdx.x; q < EV_TILE / 4; q += BIN_THREADS) ((sort_v4u *)smem)[q] = from[q];
+    // (LDS only, as in k_bin_build2; the stores above have waited for their loads)
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    L.seg = (const uint32_t *)smem;
+    L.seg_first = (uint32_t)(my_tile * EV_TILE);
+    L.seg_len = EV_TILE;
+    L.n0 = w.x;
+    L.n1 = w.y;
+  }
   if (d == 0) A.ctl[CTL_PAIRS] += W / 2;
   const double u = draw_at(A.s_rand, A.rng_inc, A.rng_aff, d);
   PairInfo R;
   R.have = false; R.off = 2; R.prob = 0; R.j = R.k = 0;
-  if (d < (cfg.n_sd + 1) / 2) R = pair_prob_body<KERNEL, false>(cfg, A, d, W, 0.0);
+  if (d < (cfg.n_sd + 1) / 2) R = pair_prob_body<KERNEL, false>(cfg, A, d, W, 0.0, &L);
   double p = R.prob;
   if (p != 0) p /= (double)cfg.substeps;  // collision.py:279
   pair_update_body<false>(cfg, A, d, d < W / 2, p, u, 0.0, true, R.off, R.j, R.k, 2 * d + R.off,
@@ -927,7 +983,9 @@ extern "C" int sdm_debug_pair_occupancy(void) {
 template <int KERNEL, bool BREAKUP>
 __global__ void __launch_bounds__(SDM_BLOCK) k_pair_prob(sdm_step_cfg cfg, FusedArgs A) {
   const int64_t W = A.ctl[CTL_WORK];
-  const int64_t d = TID();
+  // (k_pair_update needs no counterpart: everything it reads of this kernel is by pair slot)
+  const int64_t d = (int64_t)pair_block(A, blockIdx.x, gridDim.x, SDM_BLOCK) * SDM_BLOCK +
+                    threadIdx.x;
   const double u_b = 0.0;  // breakup parameters are evaluated in k_pair_update
   PairInfo R;
   R.have = false; R.prob = 0; R.cid_j = 0; R.dt_optimal = INFINITY; R.off = 2;
@@ -1271,9 +1329,9 @@ __global__ void __launch_bounds__(SDM_BLOCK) k_pair_update(sdm_step_cfg cfg, Fus
   __shared__ u128 lds[2];
   const int64_t W = A.ctl[CTL_WORK];
   const int64_t d = TID();
-  const double u = stream_draw(A.s_rand, A.rng_inc, A.rng_tab, &lds[0], 0, A.rng_aff);
-  const double u_b = BREAKUP ? stream_draw(A.s_rand_b, A.rng_inc, A.rng_tab, &lds[1], 0,
-                                           A.rng_aff)
+  const double u = stream_draw(blockIdx.x, A.s_rand, A.rng_inc, A.rng_tab, &lds[0], 0, A.rng_aff);
+  const double u_b = BREAKUP ? stream_draw(blockIdx.x, A.s_rand_b, A.rng_inc, A.rng_tab, &lds[1],
+                                           0, A.rng_aff)
                              : 0.0;
   const bool in_range = d < W / 2;
   // One adaptive cell: the per-cell bookkeeping of collisions_methods.py:357-374 needs the minimum
@@ -2398,6 +2456,22 @@ static int cond_sort(sdm_ctx *ctx, const sdm_step_cfg *cfg, sdm_step_state *st, 
 // fold_counters: false when further steps of the same call follow (sdm_collision_run)
 // more_follow: further steps of the same call follow (then the head of the next sub-step is
 // launched ahead of each read-back, see `launch_head`)
+// FusedArgs::walk_tile for the tables of a build: the tile-by-tile block order pays where a tile's
+// walks share a segment of successor words (SDM_OPT_WALK_LOCAL = 1: grid order, for A/B runs)
+static int walk_tile_of(const sdm_ctx *ctx, const ShuffleViews &views) {
+  static_assert(EV_TILE % (2 * BIN_THREADS) == 0 && EV_TILE % (2 * SDM_BLOCK) == 0 &&
+                    EV_TILE_BIG % (2 * SDM_BLOCK) == 0 && EV_TILE % 4 == 0,
+                "a pair workgroup's positions lie in one tile");
+  return views.fmt == SDM_REC_CHAIN && !ctx->opt_no_walk_local ? views.tile : 0;
+}
+
+// tests: out[b] = walk_block_map(b, n_blocks, g) for every block of a grid
+extern "C" int sdm_debug_walk_block_map(int n_blocks, int g, int *out) {
+  ARG_TRY(n_blocks >= 0 && g >= 1 && (out || n_blocks == 0));
+  for (int b = 0; b < n_blocks; ++b) out[b] = (int)walk_block_map((unsigned)b, (unsigned)n_blocks, (unsigned)g);
+  return SDM_OK;
+}
+
 static int collision_step(sdm_ctx *ctx, const sdm_step_cfg *cfg, sdm_step_state *st,
                           sdm_step_result *res, int flags, bool fold_counters, bool more_follow) {
   ARG_TRY(ctx && cfg && st && res);
@@ -2698,6 +2772,8 @@ static int collision_step(sdm_ctx *ctx, const sdm_step_cfg *cfg, sdm_step_state 
     A.rec_fmt = views.fmt;
     A.ovf_head = views.ovf_head;
     A.ovf_next = views.ovf_next;
+    A.walk_tile = walk_tile_of(ctx, views);
+    A.walk_tiles = views.n_tiles;
     A.idx_prev = cur;
     { int64_t *t = cur; cur = alt; alt = t; }
     ++swaps;
@@ -2719,6 +2795,8 @@ static int collision_step(sdm_ctx *ctx, const sdm_step_cfg *cfg, sdm_step_state 
       A.s_rand_b = ctx->ahead.s_rand_b;
       A.rec = ctx->ahead.rec;
       A.rec_fmt = ctx->ahead.rec_fmt;
+      A.walk_tile = ctx->ahead.walk_tile;
+      A.walk_tiles = ctx->ahead.walk_tiles;
       A.ovf_head = (const int32_t *)ctx->ahead.ovf_head;
       A.ovf_next = (const int32_t *)ctx->ahead.ovf_next;
       cur = ctx->ahead.cur;
@@ -3238,6 +3316,8 @@ static int collision_step(sdm_ctx *ctx, const sdm_step_cfg *cfg, sdm_step_state 
       A.rec_fmt = views.fmt;
       A.ovf_head = views.ovf_head;
       A.ovf_next = views.ovf_next;
+      A.walk_tile = walk_tile_of(ctx, views);
+      A.walk_tiles = views.n_tiles;
       A.idx_prev = cur;
     } else {
       rc = sdm_shuffle_async(ctx, S.shuffle, alt, cur, nullptr, st->cell_start, C, p_shuffle_len,
@@ -3443,6 +3523,8 @@ static int collision_step(sdm_ctx *ctx, const sdm_step_cfg *cfg, sdm_step_state 
     ctx->ahead.s_rand_b = A.s_rand_b;
     ctx->ahead.rec = A.rec;
     ctx->ahead.rec_fmt = A.rec_fmt;
+    ctx->ahead.walk_tile = A.walk_tile;
+    ctx->ahead.walk_tiles = A.walk_tiles;
     ctx->ahead.ovf_head = A.ovf_head;
     ctx->ahead.ovf_next = A.ovf_next;
     ctx->ahead.cur = cur;

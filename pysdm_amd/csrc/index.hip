@@ -413,6 +413,10 @@ static int shuffle_binned_async(sdm_ctx *ctx, char *scratch, int64_t *out, const
     views->ovf_head = ovf_head;
     // (SDM_REC_CHAIN: first = rec, tsucc = ovf_head, ssucc by place in the sorted array)
     views->ovf_next = fmt == SDM_REC_CHAIN ? chain + 3 * padded : ovf_next;
+    // (`first` and `ssucc` are nt whole tiles each: a pair workgroup may load the last tile's
+    // segment whole, fused.hip)
+    views->tile = tile;
+    views->n_tiles = nt;
     return SDM_OK;
   }
   {

@@ -51,10 +51,11 @@ __device__ __forceinline__ int2 ev_unpack(uint32_t w, int32_t tile_base, int32_t
 // ---- the tile sort's 16-byte stores (`loc`, the packed events).  When the sort rides in the pair
 // kernel its stores stream through the L2 the pair workgroups gather from, so their cache policy
 // is a compile-time choice: -DSORT_STORE=0 plain, 1 `nt`, 2 `sc1` (write-through, the line is
-// dropped from L2; only cheap at 16 bytes per lane).  Measurements: profiles/README.md, round 6.
+// dropped from L2; only cheap at 16 bytes per lane).  `sc1` is the default: 0.8 us per step of the
+// Shima box at 2^20 against plain, `nt` 0.2 (profiles/README.md, round 7).
 // Vector stores all three; `buf` + `at` words must be 16-byte aligned
 #ifndef SORT_STORE
-#define SORT_STORE 0
+#define SORT_STORE 2
 #endif
 typedef int32_t sort_v4i __attribute__((ext_vector_type(4)));
 typedef uint32_t sort_v4u __attribute__((ext_vector_type(4)));

@@ -57,6 +57,7 @@ struct ShuffleViews {
   const void *rec;  // array of the record type `fmt` names
   int fmt;
   const int32_t *ovf_head, *ovf_next;
+  int tile, n_tiles;  // events per tile of the build's sort; tiles the tables are padded to
 };
 
 #ifdef __HIPCC__
@@ -178,7 +179,22 @@ __device__ __forceinline__ void walk_packed2(const REC *__restrict__ rec,
 __device__ __forceinline__ uint32_t chain_word(uint32_t kind, int32_t payload) {
   return (kind << 30) | (uint32_t)payload;
 }
-// SDM_REC_CHAIN: two walks in lockstep (rec = first, ovf_head = tsucc, ovf_next = ssucc)
+// SDM_REC_CHAIN: two walks in lockstep from the words n0, n1 they stand at (tsucc, ssucc: the tables)
+__device__ __forceinline__ void walk_chain2_rest(const uint32_t *__restrict__ tsucc,
+                                                 const uint32_t *__restrict__ ssucc, uint32_t n0,
+                                                 uint32_t n1, int64_t &id0, int64_t &id1) {
+  while ((n0 | n1) >> 30) {  // both look-ups of a round are in flight together
+    const uint32_t k0 = n0 >> 30, k1 = n1 >> 30;
+    uint32_t m0 = n0, m1 = n1;
+    if (k0) m0 = (k0 == CHAIN_T ? tsucc : ssucc)[n0 & CHAIN_MAX];
+    if (k1) m1 = (k1 == CHAIN_T ? tsucc : ssucc)[n1 & CHAIN_MAX];
+    n0 = m0;
+    n1 = m1;
+  }
+  id0 = n0;
+  id1 = n1;
+}
+// ... from positions p0, p1 (rec = first, ovf_head = tsucc, ovf_next = ssucc)
 __device__ __forceinline__ void walk_chain2(const uint32_t *__restrict__ first,
                                             const uint32_t *__restrict__ tsucc,
                                             const uint32_t *__restrict__ ssucc, int32_t p0,
@@ -192,16 +208,26 @@ __device__ __forceinline__ void walk_chain2(const uint32_t *__restrict__ first,
     n0 = first[p0];
     n1 = first[p1];
   }
-  while ((n0 | n1) >> 30) {  // both look-ups of a round are in flight together
-    const uint32_t k0 = n0 >> 30, k1 = n1 >> 30;
-    uint32_t m0 = n0, m1 = n1;
-    if (k0) m0 = (k0 == CHAIN_T ? tsucc : ssucc)[n0 & CHAIN_MAX];
-    if (k1) m1 = (k1 == CHAIN_T ? tsucc : ssucc)[n1 & CHAIN_MAX];
-    n0 = m0;
-    n1 = m1;
-  }
-  id0 = n0;
-  id1 = n1;
+  walk_chain2_rest(tsucc, ssucc, n0, n1, id0, id1);
+}
+// ... from the words n0, n1 of `first`, with the places [seg_first, seg_first + seg_len) of ssucc
+// held in LDS (`seg`): a first look-up of an S word whose place lies in there - the walk's own
+// event is its position's last, 63 % of the positions, and its place is in the position's tile -
+// is taken from LDS; every other word and every later look-up goes to the tables
+__device__ __forceinline__ void walk_chain2_seg(const uint32_t *__restrict__ tsucc,
+                                                const uint32_t *__restrict__ ssucc,
+                                                const uint32_t *seg, uint32_t seg_first,
+                                                uint32_t seg_len, uint32_t n0, uint32_t n1,
+                                                int64_t &id0, int64_t &id1) {
+  const uint32_t k0 = n0 >> 30, k1 = n1 >> 30;
+  const uint32_t a0 = (n0 & CHAIN_MAX) - seg_first, a1 = (n1 & CHAIN_MAX) - seg_first;
+  const bool l0 = k0 == CHAIN_S && a0 < seg_len, l1 = k1 == CHAIN_S && a1 < seg_len;
+  uint32_t m0 = n0, m1 = n1;
+  if (k0 && !l0) m0 = (k0 == CHAIN_T ? tsucc : ssucc)[n0 & CHAIN_MAX];
+  if (k1 && !l1) m1 = (k1 == CHAIN_T ? tsucc : ssucc)[n1 & CHAIN_MAX];
+  if (l0) m0 = seg[a0];
+  if (l1) m1 = seg[a1];
+  walk_chain2_rest(tsucc, ssucc, m0, m1, id0, id1);
 }
 __device__ __forceinline__ int64_t walk_chain(const uint32_t *__restrict__ first,
                                               const uint32_t *__restrict__ tsucc,
