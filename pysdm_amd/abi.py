@@ -22,6 +22,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "sdm_hip.h")
 # the condensation path has a header of its own (implemented by libsdm_hip.so, not by the oracle)
 CONDENSATION_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "sdm_condensation.h")
+# and its formulae other than PySDM's defaults a further one (the `_f` symbols)
+CONDENSATION_FORMULAE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include",
+                                                 "sdm_condensation_formulae.h")
 # and so has the freezing path
 FREEZING_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "sdm_freezing.h")
 # and the vapour-deposition path
@@ -144,6 +147,10 @@ class ChemistryCfg(ctypes.Structure):  # == sdm_chemistry_cfg (include/sdm_chemi
         ("constants", ctypes.c_int32), ("timestep", c_f64), ("cell_volume", c_f64),
         ("H_min", c_f64), ("H_max", c_f64), ("ionic_strength_threshold", c_f64), ("rtol", c_f64),
     ]
+
+
+class CondFormulae(ctypes.Structure):  # == sdm_cond_formulae (include/sdm_condensation_formulae.h)
+    _fields_ = [("option", ctypes.c_int32 * 10), ("consts", c_f64 * 72)]
 
 
 class RelaxedVelocityCfg(ctypes.Structure):  # == sdm_relaxed_velocity_cfg
@@ -314,6 +321,7 @@ class Library:
 
 _hip_library = None
 _condensation_library = None
+_condensation_formulae_library = None
 _freezing_library = None
 _deposition_library = None
 _chemistry_library = None
@@ -336,6 +344,15 @@ def condensation_library():
         _condensation_library = Library(HIP_LIB_PATH, "the HIP kernels of pysdm_amd",
                                         header=CONDENSATION_HEADER_PATH)
     return _condensation_library
+
+
+def condensation_formulae_library():
+    """libsdm_hip.so bound to include/sdm_condensation_formulae.h (same file, same contexts)"""
+    global _condensation_formulae_library  # pylint: disable=global-statement
+    if _condensation_formulae_library is None:
+        _condensation_formulae_library = Library(HIP_LIB_PATH, "the HIP kernels of pysdm_amd",
+                                                 header=CONDENSATION_FORMULAE_HEADER_PATH)
+    return _condensation_formulae_library
 
 
 def freezing_library():

@@ -21,7 +21,8 @@ from .. import chemistry as chem
 from .. import deposition as dep
 from .. import freezing as frz
 from .. import seeding as seed
-from ..condensation import check_formulae, condensation_call, constants_of
+from ..condensation import (check_formulae, condensation_call, constants_of,
+                            critical_volume_call, temperature_pressure_rh_call)
 from ..displacement import SCHEMES
 from ..formulae import Formulae
 from .storage import storage_class_for
@@ -407,7 +408,8 @@ def backend_class_for(engine_getter, name, doc=None):  # pylint: disable=too-man
         # ---- condensation (condensation_methods.py; include/sdm_condensation.h) -------------------
         def make_condensation_solver(self, timestep, n_cell, *, dt_range, adaptive, fuse,
                                      multiplier, RH_rtol, max_iters):
-            """the solver's parameters (the whole solver runs in `sdm_condensation`); the checks
+            """the solver's parameters (the whole solver runs in `sdm_condensation`, or in
+            `sdm_condensation_f` where the formulae are not PySDM's defaults); the checks
             of make_adapt_substeps (condensation_methods.py:181-188)"""
             check_formulae(self.formulae)
             if not isinstance(multiplier, int):
@@ -672,10 +674,10 @@ def backend_class_for(engine_getter, name, doc=None):  # pylint: disable=too-man
             return constants_of(self.formulae, mixed_phase=self._mixed_phase())
 
         def temperature_pressure_rh(self, *, rhod, thd, water_vapour_mixing_ratio, T, p, RH):
-            self.engine.call_condensation(
-                "sdm_temperature_pressure_rh", rhod.data, thd.data,
-                water_vapour_mixing_ratio.data, T.data, p.data, RH.data, int(T.shape[0]),
-                self._ambient_consts())
+            # (the `_f` symbol where the saturation vapour pressure is not PySDM's default)
+            temperature_pressure_rh_call(
+                self.engine, self.formulae, rhod.data, thd.data, water_vapour_mixing_ratio.data,
+                T.data, p.data, RH.data, int(T.shape[0]), mixed_phase=self._mixed_phase())
 
         def air_density(self, *, output, rhod, water_vapour_mixing_ratio):
             self.engine.call_condensation("sdm_air_density", output.data, rhod.data,
@@ -687,9 +689,11 @@ def backend_class_for(engine_getter, name, doc=None):  # pylint: disable=too-man
                                           self._ambient_consts())
 
         def critical_volume(self, *, v_cr, kappa, f_org, v_dry, v_wet, T, cell):
-            self.engine.call_condensation(
-                "sdm_critical_volume", v_cr.data, kappa.data, f_org.data, v_dry.data, v_wet.data,
-                T.data, cell.data, int(v_cr.shape[0]), self._ambient_consts())
+            # (the `_f` symbol where surface tension or hygroscopicity is not PySDM's default)
+            critical_volume_call(
+                self.engine, self.formulae, v_cr.data, kappa.data, f_org.data, v_dry.data,
+                v_wet.data, T.data, cell.data, int(v_cr.shape[0]),
+                mixed_phase=self._mixed_phase())
 
         def reynolds_number(self, *, output, cell_id, dynamic_viscosity, density, radius,
                             velocity_wrt_air):

@@ -23,6 +23,8 @@ class Engine:
     handle = None
     # the implementation of include/sdm_condensation.h that goes with `library` (same contexts)
     condensation_library = None
+    # likewise include/sdm_condensation_formulae.h (the `_f` symbols: non-default formulae)
+    condensation_formulae_library = None
     # likewise include/sdm_freezing.h
     freezing_library = None
     # likewise include/sdm_deposition.h
@@ -82,6 +84,14 @@ class Engine:
             raise NotImplementedError(f"engine `{self.name}` has no condensation library")
         self._before_call()
         self.condensation_library.invoke(symbol, self.handle, args)
+
+    def call_condensation_formulae(self, symbol, *args):
+        """a symbol of include/sdm_condensation_formulae.h"""
+        if self.condensation_formulae_library is None:
+            raise NotImplementedError(
+                f"engine `{self.name}` has no library for condensation with non-default formulae")
+        self._before_call()
+        self.condensation_formulae_library.invoke(symbol, self.handle, args)
 
     def call_freezing(self, symbol, *args):
         """a symbol of include/sdm_freezing.h"""
@@ -145,6 +155,7 @@ class HipEngine(Engine):
         self.torch = torch
         self.library = abi.hip_library()
         self.condensation_library = abi.condensation_library()
+        self.condensation_formulae_library = abi.condensation_formulae_library()
         self.freezing_library = abi.freezing_library()
         self.deposition_library = abi.deposition_library()
         self.chemistry_library = abi.chemistry_library()

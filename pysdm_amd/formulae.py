@@ -3,8 +3,8 @@ stand-in for PySDM's own where PySDM is absent; under PySDM the real one is pass
 
 Collision-path subset of PySDM/formulae.py:27-67 (same keyword names: `seed`, `constants`,
 `terminal_velocity`, `fragmentation_function`, `handle_all_breakups`,
-`particle_shape_and_density`, `particle_advection`), the options of the condensation path (defaults
-only) and of the freezing path (`particle_shape_and_density="MixedPhaseSpheres"`,
+`particle_shape_and_density`, `particle_advection`), the options of the condensation path (the
+choices of pysdm_amd/physics/condensation_formulae.py `CHOICES` but `HOST_REFUSED`) and of the freezing path (`particle_shape_and_density="MixedPhaseSpheres"`,
 `heterogeneous_ice_nucleation_rate`, `homogeneous_ice_nucleation_rate`) and of vapour deposition on
 ice (`diffusion_ice_capacity`, `diffusion_ice_kinetics`, `latent_heat_sublimation`,
 `diffusion_coordinate="WaterMass"`); aqueous chemistry has no options, only `trivia` entries and
@@ -15,6 +15,7 @@ from types import SimpleNamespace
 
 import numpy as np
 
+from .physics import condensation_formulae as _cond
 from .physics import constants as _const
 
 
@@ -46,14 +47,26 @@ _FINITE = {
 }
 PARTICLE_SHAPES = ("LiquidSpheres", "MixedPhaseSpheres")
 # the choices the deposition path implements (pysdm_amd/deposition.py), PySDM's default first.
-# `diffusion_coordinate` is shared with condensation, which implements the logarithm only
-# (condensation.check_formulae goes on refusing "WaterMass")
+# `diffusion_coordinate` is shared with condensation, whose `check_formulae` goes on refusing
+# "WaterMass" (the library's general kernel serves it: condensation.descriptor_of)
 DEPOSITION_OPTIONS = {
     "diffusion_ice_capacity": ("Spherical", "Columnar"),
     "diffusion_ice_kinetics": ("Standard", "Neglect"),
     "latent_heat_sublimation": ("MurphyKoop2005",),
 }
 DIFFUSION_COORDINATES = ("WaterMassLogarithm", "WaterMass")
+
+
+def check_condensation_constants(option, value, constants):
+    """the assertions the reference's classes make on the constants when constructed (finite
+    sgm_org / delta_min / RUEHL_*, dv_pk05 == 0 for LoweEtAl2019), naming option and constant"""
+    for name in _cond.FINITE.get((option, value), ()):
+        if not math.isfinite(getattr(constants, name, math.nan)):
+            raise NotImplementedError(f"{option}={value!r} needs the constant {name} "
+                                      f"(pass constants={{'{name}': ...}})")
+    for name in _cond.ZERO.get((option, value), ()):
+        if getattr(constants, name, math.nan) != 0:
+            raise ValueError(f"{option}={value!r} needs the constant {name} to be 0")
 
 
 class _Trivia:  # PySDM/physics/trivia.py:19-28
@@ -160,17 +173,17 @@ class Formulae:  # pylint: disable=too-few-public-methods,too-many-arguments
         if particle_shape_and_density not in PARTICLE_SHAPES:
             raise NotImplementedError(
                 f"particle_shape_and_density={particle_shape_and_density!r}")
-        # the condensation path supports PySDM's defaults only (pysdm_amd/condensation.py)
+        # the condensation path: any choice of `CHOICES`, freely combined (pysdm_amd/condensation.py)
         for option, value in condensation_options.items():
             if option not in CONDENSATION_DEFAULTS:
                 raise TypeError(f"Formulae got an unexpected keyword argument '{option}'")
-            if option == "diffusion_coordinate" and value in DIFFUSION_COORDINATES:
-                continue
-            if value != CONDENSATION_DEFAULTS[option]:
+            allowed = _cond.CHOICES.get(option, (CONDENSATION_DEFAULTS[option],))
+            if value not in allowed:
                 raise NotImplementedError(f"{option}={value!r}")
-        for option, value in CONDENSATION_DEFAULTS.items():
-            setattr(self, option,
-                    SimpleNamespace(__name__=condensation_options.get(option, value)))
+            # (the coordinate is shared with deposition, which serves "WaterMass")
+            if option != "diffusion_coordinate" and value in _cond.HOST_REFUSED.get(option, ()):
+                raise NotImplementedError(
+                    f"{option}={value!r}: served by the library, not yet through Formulae")
         for option, value in (("diffusion_ice_capacity", diffusion_ice_capacity),
                               ("diffusion_ice_kinetics", diffusion_ice_kinetics),
                               ("latent_heat_sublimation", latent_heat_sublimation)):
@@ -185,7 +198,13 @@ class Formulae:  # pylint: disable=too-few-public-methods,too-many-arguments
             if not k.startswith("_") and isinstance(getattr(_const, k), (int, float))
         }
         values.update(constants or {})
+        if "water_molar_volume" not in (constants or {}):  # constants_defaults.py:770
+            values["water_molar_volume"] = values["Mv"] / values["rho_w"]
         self.constants = SimpleNamespace(**values)
+        for option, default in CONDENSATION_DEFAULTS.items():
+            value = condensation_options.get(option, default)
+            check_condensation_constants(option, value, self.constants)
+            setattr(self, option, _cond.make_option(option, value, self.constants))
         self.seed = seed if seed is not None else _const.default_random_seed
         self.fastmath = fastmath
         self.fragmentation_function = fragmentation_function

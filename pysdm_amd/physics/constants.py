@@ -162,6 +162,86 @@ H_u = M / p_STP
 dT_u = 1.0
 pH_w = 7
 
+# condensation with non-default formulae (pysdm_amd/condensation.py, include/
+# sdm_condensation_formulae.h): the organic-film surface tensions (Ovadnevaite et al. 2017, Ruehl
+# et al. 2016: the film's parameters depend on the organic species and have no default), the
+# saturation vapour pressures of August-Roche-Magnus, Bolton 1980, Lowe 1977, Murphy & Koop 2005
+# and Wexler 1976, the latent heat, diffusivity and conductivity of Lowe et al. 2019, the
+# diffusivity exponent of Tracy, Welch & Porter, the fits of Grabowski et al. 2011, the Pruppacher &
+# Klett 2005 jump length and the ventilation coefficients of Froessling 1938 and Pruppacher &
+# Rasmussen 1979 (PySDM/physics/constants_defaults.py:90,111-117,158-171,207-236,251-275,298-305,
+# 557-601,638-673,770, written as the doubles it arrives at)
+ONE_HALF = 1 / 2
+N_A = 6.02214076e+23
+water_molar_volume = 1.8015270337240393e-05
+sgm_org = math.nan
+delta_min = math.nan
+RUEHL_nu_org = math.nan
+RUEHL_A0 = math.nan
+RUEHL_C0 = math.nan
+RUEHL_m_sigma = math.nan
+RUEHL_sgm_min = math.nan
+ARM_C1 = 610.9399999999999
+ARM_C2 = 17.625
+ARM_C3 = 243.04
+B80W_G0 = 611.2
+B80W_G1 = 17.67
+B80W_G2 = 243.5
+L77W_A0 = 610.7799961000001
+L77W_A1 = 44.36518521
+L77W_A2 = 1.4289458050000001
+L77W_A3 = 0.026506484709999997
+L77W_A4 = 0.0003031240396
+L77W_A5 = 2.034080948e-06
+L77W_A6 = 6.136820928999999e-09
+MK05_LIQ_C1 = 1.0
+MK05_LIQ_C2 = 54.842763
+MK05_LIQ_C3 = 6763.22
+MK05_LIQ_C4 = 4.21
+MK05_LIQ_C5 = 1.0
+MK05_LIQ_C6 = 0.000367
+MK05_LIQ_C7 = 0.0415
+MK05_LIQ_C8 = 218.8
+MK05_LIQ_C9 = 53.878
+MK05_LIQ_C10 = 1331.22
+MK05_LIQ_C11 = 9.44523
+MK05_LIQ_C12 = 1.0
+MK05_LIQ_C13 = 0.014025
+W76W_G0 = -2991.2729
+W76W_G1 = -6017.0128
+W76W_G2 = 18.87643854
+W76W_G3 = -0.028354721
+W76W_G4 = 1.7838301e-05
+W76W_G5 = -8.4150417e-10
+W76W_G6 = 4.4412543e-13
+W76W_G7 = 2.858487
+W76W_G8 = 1.0
+one_kelvin = 1.0
+l_l19_a = 0.167
+l_l19_b = 0.000365
+d_l19_a = 2.11e-05
+d_l19_b = 1.94
+k_l19_a = 0.0042
+k_l19_b = 1.0456
+k_l19_c = 0.017
+D_exp = 1.81
+diffusion_thermics_D_G11_A = 1e-05
+diffusion_thermics_D_G11_B = 0.015
+diffusion_thermics_D_G11_C = -1.9
+diffusion_thermics_K_G11_A = 1.5e-11
+diffusion_thermics_K_G11_B = -4.8e-08
+diffusion_thermics_K_G11_C = 0.0001
+diffusion_thermics_K_G11_D = -0.00039
+dv_pk05 = 0.0
+FROESSLING_1938_A = 1
+FROESSLING_1938_B = 0.276
+PRUPPACHER_RASMUSSEN_1979_XTHRES = 1.4
+PRUPPACHER_RASMUSSEN_1979_CONSTSMALL = 1.0
+PRUPPACHER_RASMUSSEN_1979_COEFFSMALL = 0.108
+PRUPPACHER_RASMUSSEN_1979_POWSMALL = 2.0
+PRUPPACHER_RASMUSSEN_1979_CONSTBIG = 0.78
+PRUPPACHER_RASMUSSEN_1979_COEFFBIG = 0.308
+
 
 def namespace(overrides=None):
     """the numeric constants of this module as one namespace, optionally with overrides"""

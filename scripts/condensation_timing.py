@@ -13,6 +13,13 @@ The serial sum's share: run once with the product library and once with the meas
     SDM_HIP_LIB=build_variants/libsdm_cond_serial2.so python scripts/condensation_timing.py
 
 the difference of the two times is the cost of one serial chain per pass.
+
+`--formulae` picks what is timed: `default` (PySDM's default formulae through `sdm_condensation`),
+`default-through-general-kernel` (the same formulae through `sdm_condensation_f`: what the
+option switches, the staged f_org / Reynolds columns and the larger kernel cost by themselves),
+`lowe2019` (organic film of Ovadnevaite, Lowe et al. 2019 kinetics, thermics and latent heat,
+August-Roche-Magnus) and `ventilated` (Pruppacher & Rasmussen 1979, Fick, Grabowski et al. 2011
+thermics, Murphy & Koop 2005, constant latent heat), on the same state.
 """
 import argparse
 import json
@@ -23,6 +30,19 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+FORMULAE = {
+    "default": {},
+    "default-through-general-kernel": {},
+    "lowe2019": {"surface_tension": "CompressedFilmOvadnevaite",
+                 "diffusion_kinetics": "LoweEtAl2019", "diffusion_thermics": "LoweEtAl2019",
+                 "latent_heat_vapourisation": "Lowe2019",
+                 "saturation_vapour_pressure": "AugustRocheMagnus"},
+    "ventilated": {"ventilation": "PruppacherAndRasmussen1979", "drop_growth": "Fick",
+                   "diffusion_thermics": "GrabowskiEtAl2011",
+                   "saturation_vapour_pressure": "MurphyKoop2005",
+                   "latent_heat_vapourisation": "Constant"},
+}
 
 
 def state(cells, per_cell, seed=1):
@@ -53,7 +73,8 @@ def state(cells, per_cell, seed=1):
     return dict(n_cell=n_cell, n_sd=n_sd, cell_start=cell_start, idx=idx, vdry=vdry, kappa=kappa,
                 water_mass=water_mass, multiplicity=rng.integers(10 ** 6, 10 ** 8, n_sd),
                 rhod=rhod, thd=thd, qv=qv, v_cr=k.PI_4_3 * r_cr ** 3,
-                air_density=rhod * (1 + qv), eta=np.full(n_cell, 1.8e-5))
+                air_density=rhod * (1 + qv), eta=np.full(n_cell, 1.8e-5),
+                f_org=rng.uniform(0, 1, n_sd), reynolds_number=rng.uniform(0, 1, n_sd) ** 8 * 300)
 
 
 def main():
@@ -63,6 +84,7 @@ def main():
     parser.add_argument("--steps", type=int, default=5)
     parser.add_argument("--warmup", type=int, default=1)
     parser.add_argument("--dt", type=float, default=1.0)
+    parser.add_argument("--formulae", choices=sorted(FORMULAE), default="default")
     args = parser.parse_args()
 
     import torch  # pylint: disable=import-outside-toplevel
@@ -81,7 +103,16 @@ def main():
     success = up(np.zeros(n_cell, dtype=np.uint8))
     pthd, pqv = up(s["thd"]), up(s["qv"])
     cell_order = up(np.arange(n_cell, dtype=np.int64))
-    formulae = Formulae()
+    # (a choice `Formulae` refuses travels in an explicit descriptor)
+    from pysdm_amd.condensation import descriptor_of  # pylint: disable=import-outside-toplevel
+    from pysdm_amd.physics.condensation_formulae import HOST_REFUSED  # pylint: disable=import-outside-toplevel
+
+    choices = FORMULAE[args.formulae]
+    formulae = Formulae(constants={"sgm_org": 0.04, "delta_min": 1e-10},
+                        **{option: choice for option, choice in choices.items()
+                           if choice not in HOST_REFUSED.get(option, ())})
+    descriptor = descriptor_of(choices, formulae.constants)
+    general = args.formulae == "default-through-general-kernel"
     times, substeps = [], []
     for step in range(args.warmup + args.steps):
         # a kinematic step's prediction: 0.05 K cooling, 0.1 % more vapour
@@ -95,11 +126,13 @@ def main():
             vdry=d["vdry"], idx=d["idx"], rhod=d["rhod"], thd=d["thd"],
             water_vapour_mixing_ratio=d["qv"], dv=1.0, prhod=d["rhod"], pthd=pthd,
             predicted_water_vapour_mixing_ratio=pqv, kappa=d["kappa"],
-            f_org=eng.zeros(s["n_sd"], np.float64), rtol_x=1e-6, rtol_thd=1e-6,
+            f_org=d["f_org"], rtol_x=1e-6, rtol_thd=1e-6,
             timestep=args.dt, counters=counters, cell_order=cell_order, RH_max=RH_max,
-            success=success, reynolds_number=None, air_density=d["air_density"],
+            success=success, reynolds_number=d["reynolds_number"],
+            air_density=d["air_density"],
             air_dynamic_viscosity=d["eta"], dt_range=(1e-4, args.dt), adaptive=True, fuse=32,
-            multiplier=2, RH_rtol=1e-7, max_iters=16)
+            multiplier=2, RH_rtol=1e-7, max_iters=16, general=general,
+            descriptor=descriptor)
         stop.record()
         stop.synchronize()
         if not bool(success.all()):
@@ -111,6 +144,7 @@ def main():
             substeps.append(eng.download(counters["n_substeps"]))
     n = np.stack(substeps)
     print(json.dumps({
+        "formulae": args.formulae,
         "library": os.path.basename(os.environ.get("SDM_HIP_LIB") or "libsdm_hip.so"),
         "cells": n_cell, "per_cell": args.per_cell, "n_sd": s["n_sd"], "dt": args.dt,
         "ms_per_step_median": float(np.median(times)), "ms_per_step": [round(t, 3) for t in times],
