@@ -406,6 +406,13 @@ int sdm_reduce_f64(sdm_ctx *ctx, int kind, const double *a, int64_t n, double *r
 #define SDM_VELOCITY_TERMINAL 0
 #define SDM_VELOCITY_MOMENTUM 1
 
+/* the law behind SDM_VELOCITY_TERMINAL (Formulae(terminal_velocity=...) of the reference) */
+#define SDM_VELOCITY_LAW_GUNN_KINZER 0  /* the table gk_a / gk_b, as sdm_interpolation */
+#define SDM_VELOCITY_LAW_ROGERS_YAU 1   /* as sdm_terminal_velocity ; velocity_params = its consts[5] */
+#define SDM_VELOCITY_LAW_POWER_SERIES 2 /* as sdm_power_series ; velocity_params = velocity_terms
+                                           prefactors, then velocity_terms powers */
+#define SDM_VELOCITY_MAX_TERMS 16       /* the cap of sdm_power_series */
+
 typedef struct sdm_step_cfg {
   int64_t n_sd, n_cell, n_attr;
   double dt, dv;
@@ -441,6 +448,12 @@ typedef struct sdm_step_cfg {
    * like every extensive attribute.                                                          */
   int32_t velocity_source;
   int32_t momentum_attr;
+  /* SDM_VELOCITY_LAW_* (0 = the table: a zero-initialised description means what it always
+   * meant); velocity_terms: terms of the power series, 0..SDM_VELOCITY_MAX_TERMS.  The numbers
+   * travel in sdm_step_state.velocity_params.  No range check for the closed forms, as in the
+   * reference.  Ignored with SDM_VELOCITY_MOMENTUM, as the table is.                          */
+  int32_t velocity_law;
+  int32_t velocity_terms;
 } sdm_step_cfg;
 
 /* ---- sharding of a multi-cell domain over several processes (one per GPU) -------------------
@@ -544,6 +557,11 @@ typedef struct sdm_step_state {
    * one place the reference reads a cell id by RAW id - `normalize` indexes cell_id with the pair
    * number (collisions_methods.py:430-442) - needs every id's own cell: this column.  NULL = cell_id */
   const int64_t *cell_id_by_id;
+  /* device doubles of the closed-form fall-velocity laws (sdm_step_cfg.velocity_law): Rogers-Yau:
+   * 5, in the order sdm_terminal_velocity takes them; power series: 2 * velocity_terms, the
+   * prefactors first, then the powers, as sdm_power_series takes them.  Like the table it may be
+   * NULL where the set-up needs no fall velocity (u = 0 then).  Not read with law 0.           */
+  const double *velocity_params;
 } sdm_step_state;
 
 typedef struct sdm_step_result {

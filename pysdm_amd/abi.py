@@ -44,6 +44,9 @@ c_i64, c_f64, c_int, c_ptr, c_u64 = (ctypes.c_int64, ctypes.c_double, ctypes.c_i
 
 
 VELOCITY_TERMINAL, VELOCITY_MOMENTUM = 0, 1  # SDM_VELOCITY_* of include/sdm_hip.h
+# SDM_VELOCITY_LAW_*, by the names of pysdm_amd.terminal_velocity.LAWS
+VELOCITY_LAWS = {"GunnKinzer1949": 0, "RogersYau": 1, "PowerSeries": 2}
+VELOCITY_MAX_TERMS = 16
 
 
 # ---- the structs of the fused entry points (layout checked against the header in tests/test_abi.py)
@@ -64,6 +67,7 @@ class StepCfg(ctypes.Structure):  # == sdm_step_cfg
         ("max_multiplicity", c_i64), ("rng_state_inc", c_u64 * 4),
         ("gk_table_len", c_i64), ("gk_factor", c_f64),
         ("velocity_source", ctypes.c_int32), ("momentum_attr", ctypes.c_int32),
+        ("velocity_law", ctypes.c_int32), ("velocity_terms", ctypes.c_int32),
     ]
 
 
@@ -79,7 +83,7 @@ class StepState(ctypes.Structure):  # == sdm_step_state
         ("cell_owned", c_ptr), ("exchange", c_ptr), ("exchange_user", c_ptr),
         ("xchg_cells", c_ptr), ("xchg_idx", c_ptr),
         ("shard_rank", ctypes.c_int32), ("shard_world", ctypes.c_int32),
-        ("cell_id_by_id", c_ptr),
+        ("cell_id_by_id", c_ptr), ("velocity_params", c_ptr),
     ]
 
 

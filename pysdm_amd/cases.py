@@ -116,10 +116,12 @@ def initial_state(name, n_sd=None, dv=None, ids_by_cell=False):
 
 
 def make_box(engine, name, *, n_sd=None, adaptive=None, route="fused", seed=44, dt=None,
-             thin=None, grid=None, read_back=True, dv=None, ids_by_cell=False, **setup_options):
+             thin=None, grid=None, read_back=True, dv=None, ids_by_cell=False,
+             terminal_velocity="GunnKinzer1949", **setup_options):
     """a CollisionRunner for configuration `name`.  `thin` (a cell volume per 2^16
     super-droplets) replaces the multiplicities by 1, 2, 3, 1, ... so that super-droplets die;
     `grid` turns a box configuration into a multi-cell one with uniform-random cell ids;
+    `terminal_velocity`: a law's name or object (pysdm_amd.terminal_velocity);
     `setup_options` go to the CollisionSetup (substeps, croupier, optimized_random, ...)"""
     cfg = CONFIGS[name]
     if grid is not None:
@@ -141,7 +143,7 @@ def make_box(engine, name, *, n_sd=None, adaptive=None, route="fused", seed=44, 
     dv_cell = dv / population.n_cell
     return CollisionRunner(population, cfg["make"](adaptive, seed=seed, **setup_options),
                            dt=dt or cfg.get("dt", 1.0), dv=dv_cell, route=route,
-                           read_back=read_back)
+                           read_back=read_back, terminal_velocity=terminal_velocity)
 
 
 def single_eddy_courant(grid, size, dt, w_max=0.6):
@@ -160,7 +162,8 @@ def single_eddy_courant(grid, size, dt, w_max=0.6):
 
 
 def make_kinematic_flow(engine, *, n_sd=2**22, grid=(32, 32), size=(1500.0, 1500.0), dt=5.0,
-                        route="fused", seed=44, sedimentation=True):
+                        route="fused", seed=44, sedimentation=True,
+                        terminal_velocity="GunnKinzer1949"):
     """configs[3] with the step that precedes collisions in the 2-D kinematic set-up:
     displacement (single-eddy flow + sedimentation) followed by adaptive Geometric coalescence.
     Returns (displacement runner, collision runner) sharing one population"""
@@ -179,10 +182,11 @@ def make_kinematic_flow(engine, *, n_sd=2**22, grid=(32, 32), size=(1500.0, 1500
                             cell_id=cell_id, grid=grid, cell_origin=cell_origin,
                             position_in_cell=position_in_cell)
     displacement = DisplacementRunner(population, dt=dt, size=size,
-                                      enable_sedimentation=sedimentation, route=route)
+                                      enable_sedimentation=sedimentation, route=route,
+                                      terminal_velocity=terminal_velocity)
     displacement.set_courant(single_eddy_courant(grid, size, dt))
     collisions = CollisionRunner(population, cfg["make"](True, seed=seed), dt=dt, dv=dv_cell,
-                                 route=route)
+                                 route=route, terminal_velocity=terminal_velocity)
     return displacement, collisions
 
 

@@ -21,7 +21,7 @@ from . import abi
 from .engine import FLOAT, INT
 from .physics import constants as const
 from .population import MOMENTUM_ROW, VELOCITY_SOURCES
-from .terminal_velocity import LAWS
+from .terminal_velocity import law_name, make_law
 
 READ_BACK, FRESH_CTL, MIRROR_VALID = 1, 2, 4
 _DEVICE_ERRORS = {1: "a cell is larger than the per-cell kernel's capacity",
@@ -82,8 +82,17 @@ class CollisionRunner:  # pylint: disable=too-many-instance-attributes
         self.gamma_hook = None  # chain route only, see pysdm_amd.chain
         self.shard = None       # set by pysdm_amd.sharding.attach
         self.counts_global_pairs = False
-        self._law_name = terminal_velocity
+        self._law_spec = terminal_velocity  # a name, or a law object with the caller's numbers
+        self._law_name = law_name(terminal_velocity)
         self._law = None
+        if (route == "fused" and velocity == "terminal" and self.descriptor["needs_gk"]
+                and self._law_name not in eng.fused_velocity_laws):
+            # such a fused step would evaluate the law it knows: it would run, and differ
+            raise NotImplementedError(
+                f"the fused collision step of engine `{eng.name}` does not evaluate the "
+                f"terminal-velocity law {self._law_name!r} (it has "
+                f"{', '.join(eng.fused_velocity_laws)}); use route='chain'")
+        self._velocity_params = None
         self._chain = None
         self._cfg = self._state = None
         self._result = abi.StepResult()
@@ -92,9 +101,10 @@ class CollisionRunner:  # pylint: disable=too-many-instance-attributes
     # ---- parts of the set-up ------------------------------------------------------------------------
     @property
     def law(self):
-        """terminal-velocity law feeding the "fall velocity" column (built on first use)"""
+        """terminal-velocity law feeding the "fall velocity" column (built on first use; both
+        routes take it from here, Rogers-Yau with the numbers of `constants`)"""
         if self._law is None:
-            self._law = LAWS[self._law_name](self.engine)
+            self._law = make_law(self._law_spec, self.engine, self.constants)
         return self._law
 
     def step_cfg(self):
@@ -130,13 +140,26 @@ class CollisionRunner:  # pylint: disable=too-many-instance-attributes
             cfg.velocity_source = abi.VELOCITY_MOMENTUM
             cfg.momentum_attr = pop.rows[MOMENTUM_ROW]
         elif desc["needs_gk"]:
-            if self._law_name != "GunnKinzer1949":
-                raise NotImplementedError("the fused step evaluates fall velocities from the "
-                                          "Gunn-Kinzer table; use route='chain' for other laws")
-            cfg.gk_table_len = self.law.length
-            cfg.gk_factor = float(self.law.factor)
+            cfg.velocity_law = abi.VELOCITY_LAWS[self._law_name]
+            if self._law_name == "GunnKinzer1949":
+                cfg.gk_table_len = self.law.length
+                cfg.gk_factor = float(self.law.factor)
+            elif self._law_name == "PowerSeries":
+                if len(self.law.powers) > abi.VELOCITY_MAX_TERMS:
+                    raise ValueError(f"a power series of at most {abi.VELOCITY_MAX_TERMS} terms")
+                cfg.velocity_terms = len(self.law.powers)
         self._cfg = cfg
         return cfg
+
+    def velocity_params(self):
+        """the numbers of a closed-form law where the library reads them (sdm_step_state.
+        velocity_params): Rogers-Yau's five constants; the prefactors, then the powers"""
+        if self._velocity_params is None:
+            law = self.law
+            numbers = (law.consts if self._law_name == "RogersYau"
+                       else np.concatenate([law.prefactors, law.powers]))
+            self._velocity_params = self.engine.upload(np.asarray(numbers, dtype=FLOAT))
+        return self._velocity_params
 
     def _step_state(self):
         pop = self.population
@@ -161,7 +184,10 @@ class CollisionRunner:  # pylint: disable=too-many-instance-attributes
                     ("ctl", pop.ctl), ("nm", pop.mirror)):
                 setattr(state, name, address(array))
             if self.descriptor["needs_gk"] and self.velocity != "momentum":
-                state.gk_a, state.gk_b = address(self.law.a), address(self.law.b)
+                if self._law_name == "GunnKinzer1949":
+                    state.gk_a, state.gk_b = address(self.law.a), address(self.law.b)
+                else:
+                    state.velocity_params = address(self.velocity_params())
             state.known_valid = -1
             if self.shard is not None:
                 self.shard.fill(state, address)

@@ -825,8 +825,7 @@ k_terminal_velocity(double *__restrict__ values, const double *__restrict__ radi
                     TermVelConsts K) {
   const int64_t i = TID();
   if (i >= n) return;
-  const double r = radius[i];
-  values[i] = r < K.k[3] ? K.k[0] * (r * r) : (r < K.k[4] ? K.k[1] * r : K.k[2] * sdm_pow(r, 0.5));
+  values[i] = rogers_yau_velocity(radius[i], K.k);
 }
 
 __global__ void __launch_bounds__(SDM_BLOCK)
@@ -834,9 +833,7 @@ k_power_series(double *__restrict__ values, const double *__restrict__ radius, i
                int num_terms, PowerSeriesTerms T) {
   const int64_t i = TID();
   if (i >= n) return;
-  double v = 0.0;
-  for (int j = 0; j < num_terms; ++j) v = v + T.prefactor[j] * sdm_pow(radius[i], T.power[j] * 3);
-  values[i] = v;
+  values[i] = power_series_velocity(radius[i], num_terms, T.prefactor, T.power);
 }
 
 extern "C" int sdm_terminal_velocity(sdm_ctx *ctx, double *values, const double *radius,

@@ -57,7 +57,16 @@ struct FusedArgs {
   int64_t *stats_n_substep;
   int64_t *collision_rate, *collision_rate_deficit, *coalescence_rate, *breakup_rate,
       *breakup_rate_deficit;
-  const double *gk_a, *gk_b;
+  // the table - or, with a closed-form law (sdm_step_cfg.velocity_law), in the table's place, the
+  // law's numbers as sdm_step_state.velocity_params lays them out.  NULL either way = the set-up
+  // needs no velocity.  A union, and sdm_step_cfg's two new words fill what was padding in front of
+  // this struct: every kernel argument lies where it lay before the laws came, so the table's
+  // kernels load their arguments as they did
+  union {
+    const double *gk_a;
+    const double *vel_params;
+  };
+  const double *gk_b;
   int64_t *ctl;
   // sharded mode (sdm_hip.h): by cell id, 1 = this process computes the cell; NULL = all
   const uint8_t *cell_owned;
@@ -230,6 +239,29 @@ __device__ __forceinline__ double norm_factor_of(const sdm_step_cfg &cfg,
                           (double)(sd_num / 2);
 }
 
+// Every kernel that reaches derive_ru exists twice: the instantiation the Gunn-Kinzer law is
+// launched with is promised velocity_law == 0 here, first thing, so the closed forms (a pow with
+// a run-time exponent: some 25 VGPRs next to the interpolation) are not compiled into it and its
+// registers, scratch and occupancy are what they were before the laws came; CLOSED = true is the
+// sibling the other laws are launched with.  collision_step() picks by cfg->velocity_law and
+// nothing else, so the promise holds.
+#define VELOCITY_LAW_PROMISE(CLOSED)                                                \
+  do {                                                                              \
+    if constexpr (!(CLOSED))                                                        \
+      __builtin_assume(cfg.velocity_law == SDM_VELOCITY_LAW_GUNN_KINZER);           \
+  } while (0)
+
+// the fall-velocity laws without a table (uniform over the launch; the numbers come through
+// scalar loads from a few words every wave shares).  The arithmetic is physics.h's, the one the
+// stage kernels k_terminal_velocity / k_power_series run
+__device__ __forceinline__ double closed_form_velocity(const sdm_step_cfg &cfg, const FusedArgs &A,
+                                                       double r) {
+  if (!A.vel_params) return 0.0;
+  if (cfg.velocity_law == SDM_VELOCITY_LAW_ROGERS_YAU) return rogers_yau_velocity(r, A.vel_params);
+  return power_series_velocity(r, cfg.velocity_terms, A.vel_params,
+                               A.vel_params + cfg.velocity_terms);
+}
+
 // `id`: the super-droplet `v` is the state of.  With SDM_VELOCITY_MOMENTUM the velocity is the
 // reference's `ratio(relative fall momentum, water mass)`, read from the SoA row as it is now (a
 // branch uniform over the launch); the radius comes from the mass either way
@@ -239,8 +271,10 @@ __device__ __forceinline__ void derive_ru(const sdm_step_cfg &cfg, const FusedAr
   v.r = radius_of_volume(volume_of_mass(v.m, cfg.rho_w), inv);
   if (cfg.velocity_source == SDM_VELOCITY_MOMENTUM)
     v.u = (A.attributes + (int64_t)cfg.momentum_attr * cfg.n_sd)[id] / fabs(v.m);
-  else
+  else if (cfg.velocity_law == SDM_VELOCITY_LAW_GUNN_KINZER)
     v.u = A.gk_a ? gk_interpolate(v.r, cfg.gk_factor, A.gk_a, A.gk_b, cfg.gk_table_len) : 0.0;
+  else
+    v.u = closed_form_velocity(cfg, A, v.r);
 }
 
 // state of super-droplet `id`: from the mirror if there is one, else from the SoA columns
@@ -816,8 +850,9 @@ __device__ __forceinline__ int pair_update_body(const sdm_step_cfg &cfg, const F
 }
 
 // ---- non-adaptive: everything about a pair in one kernel -------------------------------------
-template <int KERNEL, bool BREAKUP>
+template <int KERNEL, bool BREAKUP, bool CLOSED = false>
 __global__ void __launch_bounds__(SDM_BLOCK) k_pair_all(sdm_step_cfg cfg, FusedArgs A) {
+  VELOCITY_LAW_PROMISE(CLOSED);
   __shared__ u128 lds[2];
   const int64_t W = A.ctl[CTL_WORK];
   const unsigned lb = pair_block(A, blockIdx.x, gridDim.x, SDM_BLOCK);
@@ -906,54 +941,17 @@ __device__ long long pair_prof[PAIR_PROF_CAP * 4];
 template <int KERNEL>
 __global__ void __launch_bounds__(BIN_THREADS) PAIR_SORT_BUDGET(KERNEL)
 k_pair_all_sort(sdm_step_cfg cfg, FusedArgs A, SortAhead X) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  PAIR_PROF_ENTRY();
-  if ((int)blockIdx.x < X.n_tiles) {
-    const int64_t length = *X.p_length;
-    bin_sort_body<true>(smem, X.events, X.toff, X.jarr, X.loc, X.n_bins, nullptr, nullptr, 1,
-                        length, length, X.s_off, A.rng_inc, A.rng_tab, nullptr, A.rng_aff);
-    PAIR_PROF_EXIT(0);
-    return;
-  }
-  const int64_t W = A.ctl[CTL_WORK];
-  // (two pair workgroups per tile: block numbers 8 apart, pair_block)
-  const unsigned lb = pair_block(A, blockIdx.x - X.n_tiles, gridDim.x - X.n_tiles, BIN_THREADS);
-  const int64_t d = (int64_t)lb * BIN_THREADS + threadIdx.x;
-  // The first look-up of a walk: for the 63 % of the positions whose own event is their last it
-  // is an S word whose place lies in the position's own tile (shuffle_build.h: place = tile_first +
-  // at) - 4096 random 4-byte reads per tile into one 16-KB segment of ssucc.  The workgroup loads
-  // its tile's segment coalesced (16 bytes per lane, in flight together with the slot's words of
-  // `first`) into the dynamic LDS that only the sorting workgroups used, and the walks take that
-  // look-up from there.  Successor words from 4096-event tiles only; the tables are whole tiles.
-  WalkSeg L;
-  L.seg = nullptr; L.seg_first = L.seg_len = L.n0 = L.n1 = 0;
-  const int64_t my_tile = 2 * (int64_t)lb * BIN_THREADS / EV_TILE;
-#ifdef WALK_NO_SEG  // (tuning builds: every look-up from the tables)
-  if (false) {
-#else
-  if (A.walk_tile == EV_TILE && A.rec_fmt == SDM_REC_CHAIN && my_tile < A.walk_tiles) {  // uniform
-#endif
-    const uint2 w = *(const uint2 *)((const uint32_t *)A.rec + 2 * d);
-    const sort_v4u *from = (const sort_v4u *)((const uint32_t *)A.ovf_next + my_tile * EV_TILE);
-    for (int q = threadIdx.x; q < EV_TILE / 4; q += BIN_THREADS) ((sort_v4u *)smem)[q] = from[q];
-    // (LDS only, as in k_bin_build2; the stores above have waited for their loads)
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    L.seg = (const uint32_t *)smem;
-    L.seg_first = (uint32_t)(my_tile * EV_TILE);
-    L.seg_len = EV_TILE;
-    L.n0 = w.x;
-    L.n1 = w.y;
-  }
-  if (d == 0) A.ctl[CTL_PAIRS] += W / 2;
-  const double u = draw_at(A.s_rand, A.rng_inc, A.rng_aff, d);
-  PairInfo R;
-  R.have = false; R.off = 2; R.prob = 0; R.j = R.k = 0;
-  if (d < (cfg.n_sd + 1) / 2) R = pair_prob_body<KERNEL, false>(cfg, A, d, W, 0.0, &L);
-  double p = R.prob;
-  if (p != 0) p /= (double)cfg.substeps;  // collision.py:279
-  pair_update_body<false>(cfg, A, d, d < W / 2, p, u, 0.0, true, R.off, R.j, R.k, 2 * d + R.off,
-                          true);
-  PAIR_PROF_EXIT(1);
+  VELOCITY_LAW_PROMISE(false);
+#include "pair_all_sort_body.inc"
+}
+
+// the sibling for the closed-form laws.  It stays at one workgroup per CU: under the budget of
+// two the closed forms would spill (16 to 96 B of scratch per lane, measured), and its sort
+// workgroups then wait for a CU instead of riding along
+template <int KERNEL>
+__global__ void __launch_bounds__(BIN_THREADS)
+k_pair_all_sort_closed(sdm_step_cfg cfg, FusedArgs A, SortAhead X) {
+#include "pair_all_sort_body.inc"
 }
 
 #ifdef PAIR_PROFILE
@@ -980,8 +978,9 @@ extern "C" int sdm_debug_pair_occupancy(void) {
 #endif
 
 // ---- adaptive: probabilities first (per-cell min of the optimal dt is a global dependency) ---
-template <int KERNEL, bool BREAKUP>
+template <int KERNEL, bool BREAKUP, bool CLOSED = false>
 __global__ void __launch_bounds__(SDM_BLOCK) k_pair_prob(sdm_step_cfg cfg, FusedArgs A) {
+  VELOCITY_LAW_PROMISE(CLOSED);
   const int64_t W = A.ctl[CTL_WORK];
   // (k_pair_update needs no counterpart: everything it reads of this kernel is by pair slot)
   const int64_t d = (int64_t)pair_block(A, blockIdx.x, gridDim.x, SDM_BLOCK) * SDM_BLOCK +
@@ -1324,8 +1323,9 @@ __global__ void __launch_bounds__(SDM_BLOCK) k_cells_turn(sdm_step_cfg cfg, Fuse
   if (T.seq) publish_ctl(A.ctl, T.box, T.seq, work);
 }
 
-template <bool BREAKUP>
+template <bool BREAKUP, bool CLOSED = false>
 __global__ void __launch_bounds__(SDM_BLOCK) k_pair_update(sdm_step_cfg cfg, FusedArgs A) {
+  VELOCITY_LAW_PROMISE(CLOSED);
   __shared__ u128 lds[2];
   const int64_t W = A.ctl[CTL_WORK];
   const int64_t d = TID();
@@ -1426,9 +1426,10 @@ struct CellArgs {
 #define CELL_MARK(k)
 #endif
 
-template <int KERNEL, bool BREAKUP>
+template <int KERNEL, bool BREAKUP, bool CLOSED = false>
 __global__ void __launch_bounds__(CELL_THREADS)
 k_cell_step(sdm_step_cfg cfg, FusedArgs A, CellArgs X) {
+  VELOCITY_LAW_PROMISE(CLOSED);
   extern __shared__ __attribute__((aligned(16))) char smem[];
 #ifdef CELL_PROFILE
   __shared__ long long cell_t[9];
@@ -1750,9 +1751,10 @@ __device__ __forceinline__ int lds_exch16(uint32_t *words, int i, int v) {
 // 170 us per sub-step whatever the cell size).  With CPW = 8 a cell is one wavefront with its own
 // slice of LDS (CELL2_CAP / 8 = 704 positions); the barriers stay workgroup-wide (the cells of a
 // workgroup move in lockstep), the reductions and counters are per wavefront anyway.
-template <int KERNEL, bool BREAKUP, int CPW, int THREADS, bool TINY = false>
+template <int KERNEL, bool BREAKUP, int CPW, int THREADS, bool TINY = false, bool CLOSED = false>
 __global__ void __launch_bounds__(THREADS, TINY ? 6 : 4)
 k_cell_step2(sdm_step_cfg cfg, FusedArgs A, CellArgs X) {
+  VELOCITY_LAW_PROMISE(CLOSED);
   extern __shared__ __attribute__((aligned(16))) char smem[];
 #ifdef CELL_PROFILE
   __shared__ long long cell_t[10];
@@ -2143,7 +2145,9 @@ k_max_cell(const int64_t *__restrict__ cell_start, int64_t n_cell, int64_t *ctl,
 }
 
 // ---- breakup: dense resolution of the listed colliding pairs ----------------------------------
+template <bool CLOSED>
 __global__ void __launch_bounds__(SDM_BLOCK) k_resolve_dense(sdm_step_cfg cfg, FusedArgs A) {
+  VELOCITY_LAW_PROMISE(CLOSED);
   const int64_t l = blockIdx.x % (unsigned)A.list_nl, chunk = blockIdx.x / (unsigned)A.list_nl;
   if (blockIdx.x == 0 && threadIdx.x < LIST_NL) A.list_count_next[threadIdx.x * SDM_CNT_STRIDE] = 0;
   const int64_t n = (int64_t)A.list_count[l * SDM_CNT_STRIDE];
@@ -2180,7 +2184,9 @@ k_sort_commit(int64_t *__restrict__ idx, const int64_t *__restrict__ sorted_buf,
 
 __global__ void k_mark_unsorted(int64_t *ctl) { ctl[CTL_SORTED] = 0; }
 
+template <bool CLOSED>
 __global__ void __launch_bounds__(SDM_BLOCK) k_nm_init(sdm_step_cfg cfg, FusedArgs A) {
+  VELOCITY_LAW_PROMISE(CLOSED);
   const int64_t i = TID();
   if (i < cfg.n_sd) sd_refresh(cfg, A, i);
 }
@@ -2421,34 +2427,47 @@ static int cond_sort(sdm_ctx *ctx, const sdm_step_cfg *cfg, sdm_step_state *st, 
 
 // kernel specialisations: collision kernel kind x breakup on/off (keeps the coalescence-only
 // kernels free of the breakup code's registers)
-#define DISPATCH_PAIR(KERN, GRID)                                                              \
+#define DISPATCH_PAIR_(KERN, GRID, CF)                                                             \
   do {                                                                                         \
     const bool brk__ = cfg->enable_breakup != 0;                                               \
     switch (cfg->kernel) {                                                                     \
       case SDM_KERNEL_GOLOVIN:                                                                 \
-        if (brk__) hipLaunchKernelGGL((KERN<SDM_KERNEL_GOLOVIN, true>), GRID, blk, 0, s, *cfg, A); \
-        else hipLaunchKernelGGL((KERN<SDM_KERNEL_GOLOVIN, false>), GRID, blk, 0, s, *cfg, A);  \
+        if (brk__) hipLaunchKernelGGL((KERN<SDM_KERNEL_GOLOVIN, true, CF>), GRID, blk, 0, s, *cfg, A); \
+        else hipLaunchKernelGGL((KERN<SDM_KERNEL_GOLOVIN, false, CF>), GRID, blk, 0, s, *cfg, A);  \
         break;                                                                                 \
       case SDM_KERNEL_GEOMETRIC:                                                               \
-        if (brk__) hipLaunchKernelGGL((KERN<SDM_KERNEL_GEOMETRIC, true>), GRID, blk, 0, s, *cfg, A); \
-        else hipLaunchKernelGGL((KERN<SDM_KERNEL_GEOMETRIC, false>), GRID, blk, 0, s, *cfg, A); \
+        if (brk__) hipLaunchKernelGGL((KERN<SDM_KERNEL_GEOMETRIC, true, CF>), GRID, blk, 0, s, *cfg, A); \
+        else hipLaunchKernelGGL((KERN<SDM_KERNEL_GEOMETRIC, false, CF>), GRID, blk, 0, s, *cfg, A); \
         break;                                                                                 \
       case SDM_KERNEL_PARAMETERIZED:                                                               \
-        if (brk__) hipLaunchKernelGGL((KERN<SDM_KERNEL_PARAMETERIZED, true>), GRID, blk, 0, s, *cfg, A); \
-        else hipLaunchKernelGGL((KERN<SDM_KERNEL_PARAMETERIZED, false>), GRID, blk, 0, s, *cfg, A); \
+        if (brk__) hipLaunchKernelGGL((KERN<SDM_KERNEL_PARAMETERIZED, true, CF>), GRID, blk, 0, s, *cfg, A); \
+        else hipLaunchKernelGGL((KERN<SDM_KERNEL_PARAMETERIZED, false, CF>), GRID, blk, 0, s, *cfg, A); \
         break;                                                                                 \
       case SDM_KERNEL_SIMPLE_GEOMETRIC:                                                               \
-        if (brk__) hipLaunchKernelGGL((KERN<SDM_KERNEL_SIMPLE_GEOMETRIC, true>), GRID, blk, 0, s, *cfg, A); \
-        else hipLaunchKernelGGL((KERN<SDM_KERNEL_SIMPLE_GEOMETRIC, false>), GRID, blk, 0, s, *cfg, A); \
+        if (brk__) hipLaunchKernelGGL((KERN<SDM_KERNEL_SIMPLE_GEOMETRIC, true, CF>), GRID, blk, 0, s, *cfg, A); \
+        else hipLaunchKernelGGL((KERN<SDM_KERNEL_SIMPLE_GEOMETRIC, false, CF>), GRID, blk, 0, s, *cfg, A); \
         break;                                                                                 \
       case SDM_KERNEL_LINEAR:                                                               \
-        if (brk__) hipLaunchKernelGGL((KERN<SDM_KERNEL_LINEAR, true>), GRID, blk, 0, s, *cfg, A); \
-        else hipLaunchKernelGGL((KERN<SDM_KERNEL_LINEAR, false>), GRID, blk, 0, s, *cfg, A); \
+        if (brk__) hipLaunchKernelGGL((KERN<SDM_KERNEL_LINEAR, true, CF>), GRID, blk, 0, s, *cfg, A); \
+        else hipLaunchKernelGGL((KERN<SDM_KERNEL_LINEAR, false, CF>), GRID, blk, 0, s, *cfg, A); \
         break;                                                                                 \
       default:                                                                                 \
-        if (brk__) hipLaunchKernelGGL((KERN<SDM_KERNEL_CONSTANT, true>), GRID, blk, 0, s, *cfg, A); \
-        else hipLaunchKernelGGL((KERN<SDM_KERNEL_CONSTANT, false>), GRID, blk, 0, s, *cfg, A); \
+        if (brk__) hipLaunchKernelGGL((KERN<SDM_KERNEL_CONSTANT, true, CF>), GRID, blk, 0, s, *cfg, A); \
+        else hipLaunchKernelGGL((KERN<SDM_KERNEL_CONSTANT, false, CF>), GRID, blk, 0, s, *cfg, A); \
     }                                                                                          \
+  } while (0)
+
+// ... x the class of the fall-velocity law (VELOCITY_LAW_PROMISE; `closed` of collision_step)
+#define DISPATCH_PAIR(KERN, GRID)                                                              \
+  do {                                                                                         \
+    if (closed) DISPATCH_PAIR_(KERN, GRID, true);                                              \
+    else DISPATCH_PAIR_(KERN, GRID, false);                                                    \
+  } while (0)
+
+#define RESOLVE_DENSE_LAUNCH(GRID)                                                             \
+  do {                                                                                         \
+    if (closed) hipLaunchKernelGGL(k_resolve_dense<true>, GRID, blk, 0, s, *cfg, A);           \
+    else hipLaunchKernelGGL(k_resolve_dense<false>, GRID, blk, 0, s, *cfg, A);                 \
   } while (0)
 
 // flags: bit 0 = read the control block back at the end; bit 1 = the control block was freshly
@@ -2488,9 +2507,25 @@ static int collision_step(sdm_ctx *ctx, const sdm_step_cfg *cfg, sdm_step_state 
   ARG_TRY(!from_momentum || (cfg->momentum_attr >= 0 && cfg->momentum_attr < cfg->n_attr &&
                              cfg->momentum_attr != cfg->mass_attr));
   ARG_TRY(!from_momentum || (!st->cell_owned && !st->exchange && st->shard_world <= 1));
-  ARG_TRY(from_momentum ||
-          (cfg->kernel != SDM_KERNEL_GEOMETRIC && cfg->kernel != SDM_KERNEL_PARAMETERIZED) ||
+  // the law behind the terminal velocity (ignored with the momentum source, as the table is: the
+  // kernels then see law 0 in a copy of the description, whatever the caller left in the member)
+  sdm_step_cfg cfg_momentum;
+  if (from_momentum && cfg->velocity_law != SDM_VELOCITY_LAW_GUNN_KINZER) {
+    cfg_momentum = *cfg;
+    cfg_momentum.velocity_law = SDM_VELOCITY_LAW_GUNN_KINZER;
+    cfg = &cfg_momentum;
+  }
+  const int law = cfg->velocity_law;
+  ARG_TRY(law >= SDM_VELOCITY_LAW_GUNN_KINZER && law <= SDM_VELOCITY_LAW_POWER_SERIES);
+  ARG_TRY(law != SDM_VELOCITY_LAW_POWER_SERIES ||
+          (cfg->velocity_terms >= 0 && cfg->velocity_terms <= SDM_VELOCITY_MAX_TERMS));
+  const bool kernel_needs_velocity =
+      cfg->kernel == SDM_KERNEL_GEOMETRIC || cfg->kernel == SDM_KERNEL_PARAMETERIZED;
+  ARG_TRY(from_momentum || law != SDM_VELOCITY_LAW_GUNN_KINZER || !kernel_needs_velocity ||
           (st->gk_a && st->gk_b && cfg->gk_table_len > 0));
+  // (a series of no terms is the velocity 0 and reads nothing)
+  ARG_TRY(law == SDM_VELOCITY_LAW_GUNN_KINZER || !kernel_needs_velocity || st->velocity_params ||
+          (law == SDM_VELOCITY_LAW_POWER_SERIES && cfg->velocity_terms == 0));
   ARG_TRY(cfg->kernel >= SDM_KERNEL_GOLOVIN && cfg->kernel <= SDM_KERNEL_LINEAR);
   ARG_TRY(cfg->adaptive || cfg->substeps >= 1);
   ARG_TRY(cfg->mass_attr >= 0 && cfg->mass_attr < cfg->n_attr);
@@ -2561,8 +2596,14 @@ static int collision_step(sdm_ctx *ctx, const sdm_step_cfg *cfg, sdm_step_state 
   A.coalescence_rate = st->coalescence_rate;
   A.breakup_rate = st->breakup_rate;
   A.breakup_rate_deficit = st->breakup_rate_deficit;
-  A.gk_a = st->gk_a;
-  A.gk_b = st->gk_b;
+  // which of the two instantiations of every kernel is launched (VELOCITY_LAW_PROMISE)
+  const bool closed = law != SDM_VELOCITY_LAW_GUNN_KINZER;
+  if (closed) {
+    A.vel_params = st->velocity_params;
+  } else {
+    A.gk_a = st->gk_a;
+    A.gk_b = st->gk_b;
+  }
   A.ctl = st->ctl;
   A.cell_owned = st->cell_owned;
   A.rng_inc = rng_inc;
@@ -2607,7 +2648,8 @@ static int collision_step(sdm_ctx *ctx, const sdm_step_cfg *cfg, sdm_step_state 
   A.nm = (double *)st->nm;
   A.nm_wide = mirror_is_wide(cfg);
   if (st->nm && (flags & 2) && !(flags & 4)) {
-    hipLaunchKernelGGL(k_nm_init, dim3(grid_for(N)), blk, 0, s, *cfg, A);
+    if (closed) hipLaunchKernelGGL(k_nm_init<true>, dim3(grid_for(N)), blk, 0, s, *cfg, A);
+    else hipLaunchKernelGGL(k_nm_init<false>, dim3(grid_for(N)), blk, 0, s, *cfg, A);
     LAUNCH_CHECK();
   }
   if (C == 1 && (flags & 2)) {
@@ -2713,8 +2755,11 @@ static int collision_step(sdm_ctx *ctx, const sdm_step_cfg *cfg, sdm_step_state 
     // > 64 KiB of dynamic LDS must be opted into, per kernel and per device (one ctx = one device)
     if (!ctx->cell_attr_done) {
       const int lds = CELL_LDS_BYTES;
-#define CELL_ATTR(K, B) HIP_TRY(hipFuncSetAttribute((const void *)k_cell_step<K, B>, \
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, lds))
+#define CELL_ATTR(K, B)                                                                  \
+  HIP_TRY(hipFuncSetAttribute((const void *)k_cell_step<K, B, false>,                    \
+                              hipFuncAttributeMaxDynamicSharedMemorySize, lds));         \
+  HIP_TRY(hipFuncSetAttribute((const void *)k_cell_step<K, B, true>,                     \
+                              hipFuncAttributeMaxDynamicSharedMemorySize, lds))
       CELL_ATTR(SDM_KERNEL_GOLOVIN, false); CELL_ATTR(SDM_KERNEL_GOLOVIN, true);
       CELL_ATTR(SDM_KERNEL_GEOMETRIC, false); CELL_ATTR(SDM_KERNEL_GEOMETRIC, true);
       CELL_ATTR(SDM_KERNEL_CONSTANT, false); CELL_ATTR(SDM_KERNEL_CONSTANT, true);
@@ -2722,23 +2767,23 @@ static int collision_step(sdm_ctx *ctx, const sdm_step_cfg *cfg, sdm_step_state 
       CELL_ATTR(SDM_KERNEL_SIMPLE_GEOMETRIC, false); CELL_ATTR(SDM_KERNEL_SIMPLE_GEOMETRIC, true);
       CELL_ATTR(SDM_KERNEL_LINEAR, false); CELL_ATTR(SDM_KERNEL_LINEAR, true);
 #undef CELL_ATTR
+#define CELL2_ATTR_(K, B, CPW, T, BYTES)                                                        \
+  HIP_TRY(hipFuncSetAttribute((const void *)k_cell_step2<K, B, CPW, T, false, false>,           \
+                              hipFuncAttributeMaxDynamicSharedMemorySize, BYTES));              \
+  HIP_TRY(hipFuncSetAttribute((const void *)k_cell_step2<K, B, CPW, T, false, true>,            \
+                              hipFuncAttributeMaxDynamicSharedMemorySize, BYTES))
 #define CELL2_ATTR(K)                                                                           \
-  HIP_TRY(hipFuncSetAttribute((const void *)k_cell_step2<K, false, 1, CELL2_THREADS>,           \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, CELL2_LDS_BYTES));    \
-  HIP_TRY(hipFuncSetAttribute((const void *)k_cell_step2<K, true, 1, CELL2_THREADS>,            \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, CELL2_LDS_BYTES));    \
-  HIP_TRY(hipFuncSetAttribute((const void *)k_cell_step2<K, false, CELL2_PACK, CELL2_THREADS>,  \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, CELL2_LDS_BYTES));    \
-  HIP_TRY(hipFuncSetAttribute((const void *)k_cell_step2<K, true, CELL2_PACK, CELL2_THREADS>,   \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, CELL2_LDS_BYTES));    \
-  HIP_TRY(hipFuncSetAttribute((const void *)k_cell_step2<K, false, 1, CELL2W_THREADS>,          \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, CELL2W_LDS_BYTES));   \
-  HIP_TRY(hipFuncSetAttribute((const void *)k_cell_step2<K, true, 1, CELL2W_THREADS>,           \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, CELL2W_LDS_BYTES))
+  CELL2_ATTR_(K, false, 1, CELL2_THREADS, CELL2_LDS_BYTES);                                     \
+  CELL2_ATTR_(K, true, 1, CELL2_THREADS, CELL2_LDS_BYTES);                                      \
+  CELL2_ATTR_(K, false, CELL2_PACK, CELL2_THREADS, CELL2_LDS_BYTES);                            \
+  CELL2_ATTR_(K, true, CELL2_PACK, CELL2_THREADS, CELL2_LDS_BYTES);                             \
+  CELL2_ATTR_(K, false, 1, CELL2W_THREADS, CELL2W_LDS_BYTES);                                   \
+  CELL2_ATTR_(K, true, 1, CELL2W_THREADS, CELL2W_LDS_BYTES)
       CELL2_ATTR(SDM_KERNEL_GOLOVIN); CELL2_ATTR(SDM_KERNEL_GEOMETRIC);
       CELL2_ATTR(SDM_KERNEL_CONSTANT); CELL2_ATTR(SDM_KERNEL_PARAMETERIZED);
       CELL2_ATTR(SDM_KERNEL_SIMPLE_GEOMETRIC); CELL2_ATTR(SDM_KERNEL_LINEAR);
 #undef CELL2_ATTR
+#undef CELL2_ATTR_
       ctx->cell_attr_done = true;
     }
   }
@@ -2819,20 +2864,25 @@ static int collision_step(sdm_ctx *ctx, const sdm_step_cfg *cfg, sdm_step_state 
                       ctx->opt_cell_shape != SDM_CELL_SHAPE_512;  // (forced 512: the 704 cap)
     const dim3 grid((unsigned)(C + X.n_tail_blocks));
     const dim3 grid_p((unsigned)((C + CELL2_PACK - 1) / CELL2_PACK + X.n_tail_blocks));
+#define CELL_LAUNCH_(K, CF)                                                                       \
+  do {                                                                                        \
+    if (tiny && brk) hipLaunchKernelGGL((k_cell_step2<K, true, CELL2_PACK, CELL2_THREADS, true, CF>), grid_p, dim3(CELL2_THREADS), CELL2T_LDS_BYTES, s, *cfg, A, X); \
+    else if (tiny) hipLaunchKernelGGL((k_cell_step2<K, false, CELL2_PACK, CELL2_THREADS, true, CF>), grid_p, dim3(CELL2_THREADS), CELL2T_LDS_BYTES, s, *cfg, A, X); \
+    else if (packed && brk) hipLaunchKernelGGL((k_cell_step2<K, true, CELL2_PACK, CELL2_THREADS, false, CF>), grid_p, dim3(CELL2_THREADS), CELL2_LDS_BYTES, s, *cfg, A, X); \
+    else if (packed) hipLaunchKernelGGL((k_cell_step2<K, false, CELL2_PACK, CELL2_THREADS, false, CF>), grid_p, dim3(CELL2_THREADS), CELL2_LDS_BYTES, s, *cfg, A, X); \
+    else if (cell2w && brk) hipLaunchKernelGGL((k_cell_step2<K, true, 1, CELL2W_THREADS, false, CF>), grid, dim3(CELL2W_THREADS), CELL2W_LDS_BYTES, s, *cfg, A, X); \
+    else if (cell2w) hipLaunchKernelGGL((k_cell_step2<K, false, 1, CELL2W_THREADS, false, CF>), grid, dim3(CELL2W_THREADS), CELL2W_LDS_BYTES, s, *cfg, A, X); \
+    else if (cell2q && brk) hipLaunchKernelGGL((k_cell_step2<K, true, 1, CELL2Q_THREADS, false, CF>), grid, dim3(CELL2Q_THREADS), CELL2Q_LDS_BYTES, s, *cfg, A, X); \
+    else if (cell2q) hipLaunchKernelGGL((k_cell_step2<K, false, 1, CELL2Q_THREADS, false, CF>), grid, dim3(CELL2Q_THREADS), CELL2Q_LDS_BYTES, s, *cfg, A, X); \
+    else if (cell2 && brk) hipLaunchKernelGGL((k_cell_step2<K, true, 1, CELL2_THREADS, false, CF>), grid, dim3(CELL2_THREADS), CELL2_LDS_BYTES, s, *cfg, A, X); \
+    else if (cell2) hipLaunchKernelGGL((k_cell_step2<K, false, 1, CELL2_THREADS, false, CF>), grid, dim3(CELL2_THREADS), CELL2_LDS_BYTES, s, *cfg, A, X); \
+    else if (brk) hipLaunchKernelGGL((k_cell_step<K, true, CF>), grid, dim3(CELL_THREADS), CELL_LDS_BYTES, s, *cfg, A, X); \
+    else hipLaunchKernelGGL((k_cell_step<K, false, CF>), grid, dim3(CELL_THREADS), CELL_LDS_BYTES, s, *cfg, A, X);    \
+  } while (0)
 #define CELL_LAUNCH(K)                                                                        \
   do {                                                                                        \
-    if (tiny && brk) hipLaunchKernelGGL((k_cell_step2<K, true, CELL2_PACK, CELL2_THREADS, true>), grid_p, dim3(CELL2_THREADS), CELL2T_LDS_BYTES, s, *cfg, A, X); \
-    else if (tiny) hipLaunchKernelGGL((k_cell_step2<K, false, CELL2_PACK, CELL2_THREADS, true>), grid_p, dim3(CELL2_THREADS), CELL2T_LDS_BYTES, s, *cfg, A, X); \
-    else if (packed && brk) hipLaunchKernelGGL((k_cell_step2<K, true, CELL2_PACK, CELL2_THREADS>), grid_p, dim3(CELL2_THREADS), CELL2_LDS_BYTES, s, *cfg, A, X); \
-    else if (packed) hipLaunchKernelGGL((k_cell_step2<K, false, CELL2_PACK, CELL2_THREADS>), grid_p, dim3(CELL2_THREADS), CELL2_LDS_BYTES, s, *cfg, A, X); \
-    else if (cell2w && brk) hipLaunchKernelGGL((k_cell_step2<K, true, 1, CELL2W_THREADS>), grid, dim3(CELL2W_THREADS), CELL2W_LDS_BYTES, s, *cfg, A, X); \
-    else if (cell2w) hipLaunchKernelGGL((k_cell_step2<K, false, 1, CELL2W_THREADS>), grid, dim3(CELL2W_THREADS), CELL2W_LDS_BYTES, s, *cfg, A, X); \
-    else if (cell2q && brk) hipLaunchKernelGGL((k_cell_step2<K, true, 1, CELL2Q_THREADS>), grid, dim3(CELL2Q_THREADS), CELL2Q_LDS_BYTES, s, *cfg, A, X); \
-    else if (cell2q) hipLaunchKernelGGL((k_cell_step2<K, false, 1, CELL2Q_THREADS>), grid, dim3(CELL2Q_THREADS), CELL2Q_LDS_BYTES, s, *cfg, A, X); \
-    else if (cell2 && brk) hipLaunchKernelGGL((k_cell_step2<K, true, 1, CELL2_THREADS>), grid, dim3(CELL2_THREADS), CELL2_LDS_BYTES, s, *cfg, A, X); \
-    else if (cell2) hipLaunchKernelGGL((k_cell_step2<K, false, 1, CELL2_THREADS>), grid, dim3(CELL2_THREADS), CELL2_LDS_BYTES, s, *cfg, A, X); \
-    else if (brk) hipLaunchKernelGGL((k_cell_step<K, true>), grid, dim3(CELL_THREADS), CELL_LDS_BYTES, s, *cfg, A, X); \
-    else hipLaunchKernelGGL((k_cell_step<K, false>), grid, dim3(CELL_THREADS), CELL_LDS_BYTES, s, *cfg, A, X);    \
+    if (closed) CELL_LAUNCH_(K, true);                                                        \
+    else CELL_LAUNCH_(K, false);                                                              \
   } while (0)
     switch (cfg->kernel) {
       case SDM_KERNEL_GOLOVIN: CELL_LAUNCH(SDM_KERNEL_GOLOVIN); break;
@@ -2843,6 +2893,7 @@ static int collision_step(sdm_ctx *ctx, const sdm_step_cfg *cfg, sdm_step_state 
       default: CELL_LAUNCH(SDM_KERNEL_CONSTANT);
     }
 #undef CELL_LAUNCH
+#undef CELL_LAUNCH_
     LAUNCH_CHECK();
     return SDM_OK;
   };
@@ -3034,8 +3085,7 @@ static int collision_step(sdm_ctx *ctx, const sdm_step_cfg *cfg, sdm_step_state 
       if (cfg->enable_breakup) {
         PhaseScope ph(ctx, SDM_PHASE_PAIR_UPDATE);
         const int64_t chunks = (A.list_cap + SDM_BLOCK - 1) / SDM_BLOCK;
-        hipLaunchKernelGGL(k_resolve_dense, dim3((unsigned)(A.list_nl * chunks)), blk, 0, s, *cfg,
-                           A);
+        RESOLVE_DENSE_LAUNCH(dim3((unsigned)(A.list_nl * chunks)));
         LAUNCH_CHECK();
         std::swap(A.list_count, A.list_count_next);
       }
@@ -3378,7 +3428,11 @@ static int collision_step(sdm_ctx *ctx, const sdm_step_cfg *cfg, sdm_step_state 
         pair_prof_launch[2] = B.n_tiles;
 #endif
         const dim3 big(BIN_THREADS);
-#define PAIR_SORT(K) hipLaunchKernelGGL((k_pair_all_sort<K>), grid, big, B.lds_bytes, s, *cfg, A, X)
+#define PAIR_SORT(K)                                                                           \
+  do {                                                                                         \
+    if (closed) hipLaunchKernelGGL((k_pair_all_sort_closed<K>), grid, big, B.lds_bytes, s, *cfg, A, X); \
+    else hipLaunchKernelGGL((k_pair_all_sort<K>), grid, big, B.lds_bytes, s, *cfg, A, X);      \
+  } while (0)
         switch (cfg->kernel) {
           case SDM_KERNEL_GOLOVIN: PAIR_SORT(SDM_KERNEL_GOLOVIN); break;
           case SDM_KERNEL_GEOMETRIC: PAIR_SORT(SDM_KERNEL_GEOMETRIC); break;
@@ -3418,18 +3472,21 @@ static int collision_step(sdm_ctx *ctx, const sdm_step_cfg *cfg, sdm_step_state 
       fill_pending = false;
       {
         PhaseScope ph(ctx, SDM_PHASE_PAIR_UPDATE);
-        if (cfg->enable_breakup)
-          hipLaunchKernelGGL(k_pair_update<true>, dim3(grid_for(P)), blk, 0, s, *cfg, A);
+        if (cfg->enable_breakup && closed)
+          hipLaunchKernelGGL((k_pair_update<true, true>), dim3(grid_for(P)), blk, 0, s, *cfg, A);
+        else if (cfg->enable_breakup)
+          hipLaunchKernelGGL((k_pair_update<true, false>), dim3(grid_for(P)), blk, 0, s, *cfg, A);
+        else if (closed)
+          hipLaunchKernelGGL((k_pair_update<false, true>), dim3(grid_for(P)), blk, 0, s, *cfg, A);
         else
-          hipLaunchKernelGGL(k_pair_update<false>, dim3(grid_for(P)), blk, 0, s, *cfg, A);
+          hipLaunchKernelGGL((k_pair_update<false, false>), dim3(grid_for(P)), blk, 0, s, *cfg, A);
         LAUNCH_CHECK();
       }
     }
     if (cfg->enable_breakup) {
       PhaseScope ph(ctx, SDM_PHASE_PAIR_UPDATE);
       const int64_t chunks = (A.list_cap + SDM_BLOCK - 1) / SDM_BLOCK;
-      hipLaunchKernelGGL(k_resolve_dense, dim3((unsigned)(A.list_nl * chunks)), blk, 0, s, *cfg,
-                         A);
+      RESOLVE_DENSE_LAUNCH(dim3((unsigned)(A.list_nl * chunks)));
       LAUNCH_CHECK();
       std::swap(A.list_count, A.list_count_next);  // it left the other set of counts cleared
     }
@@ -3645,7 +3702,7 @@ extern "C" int sdm_collision_step(sdm_ctx *ctx, const sdm_step_cfg *cfg, sdm_ste
 // ordered against the caller's stream by events.
 struct GraphKey {
   sdm_step_cfg cfg;
-  const void *ptr[12];
+  const void *ptr[13];
   const void *arena;
   size_t arena_bytes;
 };
@@ -3668,9 +3725,10 @@ static int graph_replay(sdm_ctx *ctx, const sdm_step_cfg *cfg, sdm_step_state *s
   GraphKey key;
   memset(&key, 0, sizeof(key));
   key.cfg = *cfg;
-  const void *ptrs[12] = {st->idx, st->tmp_idx, st->multiplicity, st->attributes, st->cell_id,
+  const void *ptrs[13] = {st->idx, st->tmp_idx, st->multiplicity, st->attributes, st->cell_id,
                           st->cell_start, st->ctl, st->nm, st->collision_rate,
-                          st->coalescence_rate, st->breakup_rate, st->gk_a};
+                          st->coalescence_rate, st->breakup_rate, st->gk_a,
+                          st->velocity_params};
   memcpy(key.ptr, ptrs, sizeof(ptrs));
   key.arena = ctx->arena;
   key.arena_bytes = ctx->arena_bytes;

@@ -39,6 +39,22 @@ __device__ __forceinline__ double gk_interpolate(double r, double factor,
   return a[r_id] + r_rest * b[r_id];
 }
 
+// terminal_velocity_methods.py:32-48 (Rogers & Yau; k = {small k, medium k, large k, small-radius
+// limit, medium-radius limit}).  The one statement of the law: sdm_terminal_velocity, the fused
+// collision step and the relaxed-velocity step all evaluate this, so their bits agree
+__device__ __forceinline__ double rogers_yau_velocity(double r, const double *__restrict__ k) {
+  return r < k[3] ? k[0] * (r * r) : (r < k[4] ? k[1] * r : k[2] * sdm_pow(r, 0.5));
+}
+
+// terminal_velocity_methods.py:50-66 (power series in the radius: power * 3), terms left to right
+__device__ __forceinline__ double power_series_velocity(double r, int num_terms,
+                                                        const double *__restrict__ prefactor,
+                                                        const double *__restrict__ power) {
+  double v = 0.0;
+  for (int j = 0; j < num_terms; ++j) v = v + prefactor[j] * sdm_pow(r, power[j] * 3);
+  return v;
+}
+
 // collisions_methods.py:743-769, one pair
 __device__ __forceinline__ double linear_collection_efficiency(const double *__restrict__ P,
                                                                double ra, double rb,

@@ -58,8 +58,7 @@ __device__ __forceinline__ double rv_slot(const sdm_relaxed_velocity_cfg &cfg, c
   if (cfg.law == SDM_RV_LAW_GUNN_KINZER) {
     u_t = rv_table(cfg, A, r);
   } else {
-    const double *K = cfg.rogers_yau;
-    u_t = r < K[3] ? K[0] * (r * r) : (r < K[4] ? K[1] * r : K[2] * sdm_pow(r, 0.5));
+    u_t = rogers_yau_velocity(r, cfg.rogers_yau);
   }
   const double tau = cfg.constant ? cfg.c : cfg.c * signed_pow(r, 0.5);
   const double scale = sdm_exp(-cfg.dt / tau) * -1.0 + 1.0;

@@ -17,7 +17,7 @@ import numpy as np
 from . import abi
 from .engine import FLOAT, INT
 from .population import grid_strides
-from .terminal_velocity import LAWS
+from .terminal_velocity import make_law
 
 SCHEMES = {"ImplicitInSpace": 0, "ExplicitInSpace": 1}
 _EW_ADD, _EW_SUB, _EW_MUL, _EW_MOD = 0, 1, 2, 11
@@ -68,7 +68,7 @@ class DisplacementRunner:  # pylint: disable=too-many-instance-attributes
         self.whole_cells = eng.zeros((self.n_dims, n_sd), INT)
         self.strides = eng.upload(grid_strides(self.grid))
         self.ctl = eng.zeros(8, INT)
-        self.law = LAWS[terminal_velocity](eng) if enable_sedimentation else None
+        self.law = make_law(terminal_velocity, eng) if enable_sedimentation else None
         # a sharded run (pysdm_amd.sharding.attach_displacement): this process moves the
         # super-droplets of its own cells, `sdm_displacement_step_sharded`
         self.shard = None

@@ -38,6 +38,9 @@ class Engine:
     # whether the fused collision step of `library` can take the fall velocity from the
     # "relative fall momentum" row; an engine that cannot must refuse, not ignore the request
     fused_momentum_velocity = False
+    # the terminal-velocity laws (keys of pysdm_amd.terminal_velocity.LAWS) the fused collision
+    # step of `library` evaluates; a runner refuses the others where a velocity is needed
+    fused_velocity_laws = ("GunnKinzer1949",)
 
     # ---- arrays -----------------------------------------------------------------------------
     def empty(self, shape, dtype):
@@ -147,6 +150,8 @@ class HipEngine(Engine):
     name = "hip"
     # fused.hip reads the velocity from the momentum row (sdm_step_cfg.velocity_source)
     fused_momentum_velocity = True
+    # fused.hip: sdm_step_cfg.velocity_law
+    fused_velocity_laws = ("GunnKinzer1949", "RogersYau", "PowerSeries")
     _instances = {}
 
     def __init__(self, device_index):

@@ -28,8 +28,13 @@
 4. Relaxed fall velocity.  `fuse(RelaxedVelocity(...))` likewise: every call is ONE
    `sdm_relaxed_velocity_step` on PySDM's own "signed water mass" and "relative fall momentum"
    rows.  With `RelaxedVelocity` among the dynamics PySDM's "relative fall velocity" is momentum /
-   water mass; the fused collision step derives it from the radius, so `fuse(<collision
-   dynamic>)` refuses to run beside it (PySDM's own dynamic on the plugged backend does run).
+   water mass; `fuse(<collision dynamic>)` beside it reads the velocity from that row
+   (sdm_step_cfg.velocity_source) where the engine's fused step can, and refuses where it cannot.
+
+5. The fall-velocity law.  `fuse(<collision dynamic>)` evaluates the law of
+   `Formulae(terminal_velocity=...)` (`velocity_law_from_pysdm`): the Gunn-Kinzer table,
+   Rogers-Yau with the formulae's constants, or the default power series; an engine whose fused
+   step lacks the law refuses by name.
 
 PySDM itself is imported lazily: this module loads (and fails loudly) only where PySDM exists.
 PySDM's ParticleAttributes keeps the permutation index, `cell_start`, the sorted flag and the
@@ -47,6 +52,7 @@ from . import relaxed_velocity as relax
 from . import seeding as seed
 from .collisions import CollisionRunner
 from .population import Population
+from .terminal_velocity import PowerSeries, RogersYau
 
 _PRIVATE = "_ParticleAttributes__"
 
@@ -130,6 +136,23 @@ def setup_from_pysdm(dynamic, formulae):
         warn_overflows=bool(dynamic.warn_overflows),
         handle_all_breakups=bool(formulae.handle_all_breakups), seed=int(formulae.seed),
         max_multiplicity=int(dynamic.max_multiplicity))
+
+
+def velocity_law_from_pysdm(formulae):
+    """`formulae.terminal_velocity` as this package's law: the name of the table (built per
+    engine), Rogers-Yau with `formulae.constants`, or the power series with the default
+    coefficients, which is what `formulae.terminal_velocity_class(particulator)` builds"""
+    # (PySDM: the physics module of that name; this package's Formulae: the name; a formulae
+    # object that names no law has the default of both)
+    law = getattr(formulae, "terminal_velocity", "GunnKinzer1949")
+    name = law if isinstance(law, str) else getattr(law, "__name__", type(law).__name__)
+    if name == "GunnKinzer1949":
+        return name
+    if name == "RogersYau":
+        return RogersYau(constants=formulae.constants)
+    if name == "PowerSeries":
+        return PowerSeries()
+    raise NotImplementedError(f"terminal_velocity={name!r} has no counterpart in this package")
 
 
 class _AdoptedState:
@@ -250,7 +273,9 @@ class FusedCollision(Collision):
             setup = setup_from_pysdm(self.inner, part.formulae)
             self.runner = CollisionRunner(self._state.population, setup, dt=part.dt,
                                           dv=part.mesh.dv, route="fused",
-                                          constants=part.formulae.constants, velocity=velocity)
+                                          constants=part.formulae.constants, velocity=velocity,
+                                          terminal_velocity=velocity_law_from_pysdm(
+                                              part.formulae))
         self._state.before()
         self.runner.run(1)
         self._state.after()

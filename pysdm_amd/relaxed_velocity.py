@@ -24,24 +24,13 @@ from . import abi
 from .engine import FLOAT, INT
 from .physics import constants as const
 from .population import MOMENTUM_ROW
-from .terminal_velocity import LAWS, GunnKinzerTable
+from .terminal_velocity import LAWS, GunnKinzerTable, law_name
 
 ROUTES = ("fused", "stages")
 LAW_CODES = {"GunnKinzer1949": 0, "RogersYau": 1}
 STATUS_ABOVE_TOP, STATUS_WORDS = 0, 2
 # SDM_EW_* of include/sdm_hip.h
 _ADD, _SUB, _MUL, _DIV, _POW, _EXP, _ABS, _FILL = 0, 1, 2, 3, 4, 7, 8, 9
-
-
-def _law_name(law):
-    if isinstance(law, str):
-        if law not in LAWS:
-            raise ValueError(f"terminal_velocity={law!r}: one of {tuple(LAWS)}")
-        return law
-    for name, cls in LAWS.items():
-        if isinstance(law, cls):
-            return name
-    raise ValueError(f"not a terminal-velocity law: {law!r}")
 
 
 def _radius_of_water_mass(engine, out, water_mass, n, rho_w):
@@ -59,7 +48,7 @@ def init_fall_momenta(engine, water_mass, law="GunnKinzer1949", zero=False, rho_
     water_mass = np.ascontiguousarray(water_mass, dtype=float)
     if zero:
         return np.zeros_like(water_mass)
-    name = _law_name(law)
+    name = law_name(law)
     law = LAWS[name](engine) if isinstance(law, str) else law
     n = int(water_mass.shape[0])
     mass = engine.upload(np.abs(water_mass))
@@ -84,7 +73,7 @@ class RelaxedVelocityRunner:  # pylint: disable=too-many-instance-attributes
         if MOMENTUM_ROW not in population.rows or population.velocity_source != "momentum":
             raise ValueError(f"the population needs the extensive row {MOMENTUM_ROW!r} and "
                              "velocity_source='momentum'")
-        name = _law_name(terminal_velocity)
+        name = law_name(terminal_velocity)
         if route == "fused" and name == "PowerSeries":
             raise NotImplementedError("terminal_velocity='PowerSeries' is not offered on the "
                                       "fused route of RelaxedVelocityRunner; use route='stages'")

@@ -93,11 +93,14 @@ class GunnKinzerTable:
 class RogersYau:
     """Rogers & Yau eqs 8.5, 8.6, 8.8 (three radius regimes)"""
 
-    def __init__(self, engine=None):  # pylint: disable=unused-argument
-        self.consts = (const.ROGERS_YAU_TERM_VEL_SMALL_K, const.ROGERS_YAU_TERM_VEL_MEDIUM_K,
-                       const.ROGERS_YAU_TERM_VEL_LARGE_K,
-                       const.ROGERS_YAU_TERM_VEL_SMALL_R_LIMIT,
-                       const.ROGERS_YAU_TERM_VEL_MEDIUM_R_LIMIT)
+    def __init__(self, engine=None, constants=None):  # pylint: disable=unused-argument
+        """`constants`: a namespace holding the five ROGERS_YAU_TERM_VEL_* numbers (a runner's
+        `constants`, PySDM's `formulae.constants`); the module's defaults otherwise"""
+        k = const if constants is None else constants
+        self.consts = tuple(float(v) for v in (
+            k.ROGERS_YAU_TERM_VEL_SMALL_K, k.ROGERS_YAU_TERM_VEL_MEDIUM_K,
+            k.ROGERS_YAU_TERM_VEL_LARGE_K, k.ROGERS_YAU_TERM_VEL_SMALL_R_LIMIT,
+            k.ROGERS_YAU_TERM_VEL_MEDIUM_R_LIMIT))
 
     def evaluate(self, engine, out, radius, n):
         engine.call("sdm_terminal_velocity", out, radius, n, self.consts)
@@ -122,3 +125,26 @@ class PowerSeries:
 
 
 LAWS = {"GunnKinzer1949": GunnKinzerTable, "RogersYau": RogersYau, "PowerSeries": PowerSeries}
+
+
+def law_name(law):
+    """the key of LAWS for a name or a law object"""
+    if isinstance(law, str):
+        if law not in LAWS:
+            raise ValueError(f"terminal_velocity={law!r}: one of {tuple(LAWS)}")
+        return law
+    for name, cls in LAWS.items():
+        if isinstance(law, cls):
+            return name
+    raise ValueError(f"not a terminal-velocity law: {law!r}")
+
+
+def make_law(law, engine, constants=None):
+    """a law object for `engine`: `law` itself if it is one, else the law of that name (Rogers-Yau
+    with the numbers of `constants`)"""
+    if not isinstance(law, str):
+        law_name(law)
+        return law
+    if law_name(law) == "RogersYau":
+        return RogersYau(engine, constants=constants)
+    return LAWS[law](engine)
