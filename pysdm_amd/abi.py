@@ -36,6 +36,9 @@ SEEDING_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "sdm_seedi
 # and the relaxed-fall-velocity path
 RELAXED_VELOCITY_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include",
                                             "sdm_relaxed_velocity.h")
+# and the initialisation path (Koehler-equilibrium wet radii)
+INITIALISATION_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include",
+                                          "sdm_initialisation.h")
 # SDM_HIP_LIB: another build of the same library (tuning variants); still no fallback
 HIP_LIB_PATH = os.environ.get("SDM_HIP_LIB") or os.path.join(_HERE, "libsdm_hip.so")
 
@@ -331,6 +334,7 @@ _deposition_library = None
 _chemistry_library = None
 _seeding_library = None
 _relaxed_velocity_library = None
+_initialisation_library = None
 
 
 def hip_library():
@@ -402,6 +406,15 @@ def relaxed_velocity_library():
         _relaxed_velocity_library = Library(HIP_LIB_PATH, "the HIP kernels of pysdm_amd",
                                             header=RELAXED_VELOCITY_HEADER_PATH)
     return _relaxed_velocity_library
+
+
+def initialisation_library():
+    """libsdm_hip.so bound to include/sdm_initialisation.h (same file, same contexts)"""
+    global _initialisation_library  # pylint: disable=global-statement
+    if _initialisation_library is None:
+        _initialisation_library = Library(HIP_LIB_PATH, "the HIP kernels of pysdm_amd",
+                                          header=INITIALISATION_HEADER_PATH)
+    return _initialisation_library
 
 
 def pcg64_state_inc(seed):

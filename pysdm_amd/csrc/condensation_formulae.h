@@ -28,6 +28,9 @@ typedef struct cf_k {
   int32_t o[10];                 /* SDM_COND_OPT_* */
 } cf_k;
 
+/* how many choices each option has (SDM_COND_OPT_* order): a code outside [0, n) is refused */
+#define CF_N_CHOICES {2, 6, 3, 2, 3, 4, 4, 4, 3}
+
 #define CF_C(name) (k->c[SDM_COND_K_##name])
 #define CF_F(name) (k->f[SDM_COND_F_##name])
 #define CF_O(name) (k->o[SDM_COND_OPT_##name])

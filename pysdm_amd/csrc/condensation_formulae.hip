@@ -173,7 +173,7 @@ __global__ void k_critical_volume_f(double *v_cr, const double *kappa, const dou
 // the descriptor and the default path's constants as the kernels' argument; refuses codes the
 // header does not define
 int formulae_of(const double *consts, const sdm_cond_formulae *formulae, cf_k *out) {
-  static const int n_choices[SDM_COND_N_OPTS] = {2, 6, 3, 2, 3, 4, 4, 4, 3};
+  static const int n_choices[SDM_COND_N_OPTS] = CF_N_CHOICES;
   for (int i = 0; i < SDM_COND_N_OPTS; ++i)
     if (formulae->option[i] < 0 || formulae->option[i] >= n_choices[i]) return 0;
   for (int i = 0; i < SDM_COND_N_CONSTS; ++i) out->c[i] = consts[i];

@@ -8,8 +8,12 @@
  *   TOMS748_FN            the qualifiers of every function here (e.g. SDM_MATH_FN)
  *   TOMS748_ARGS          the type of the function's arguments, passed by const pointer
  *   TOMS748_EVAL(x, args) the function value at x
- * and gets `toms748_solve`.  Only the chemistry path includes it (condensation.hip keeps the
- * transcription bound to its own function).  Every loop is bounded by max_iter or a constant.
+ *   TOMS748_NAME(name)    optional: how `toms748_solve` (and its `toms748_bracket`) are named,
+ *                         for a translation unit that searches on two functions: it includes this
+ *                         file once per function, the second time with e.g. name##_wet
+ * and gets `toms748_solve`.  The chemistry path, condensation_formulae.h and the initialisation
+ * path include it (condensation.hip keeps the transcription bound to its own function).  Every
+ * loop is bounded by max_iter or a constant.
  * Where the reference warns and returns (nan, -1) - not a < b, not fa * fb < 0 - this returns NaN
  * with *iters = -1 and does not warn.
  */
@@ -23,26 +27,6 @@
 typedef struct toms748_state { double a, b, fa, fb, d, fd; } toms748_state;
 
 TOMS748_FN double toms748_abs(double x) { return x < 0 ? -x : (x == 0 ? 0.0 : x); }
-
-/* toms748.py:24-49 */
-TOMS748_FN void toms748_bracket(const TOMS748_ARGS *args, toms748_state *s, double c) {
-  const double tol = TOMS748_EPS * 2;
-  double a = s->a, b = s->b;
-  if ((b - a) < 2 * tol * a)
-    c = a + (b - a) / 2;
-  else if (c <= a + toms748_abs(a) * tol)
-    c = a + toms748_abs(a) * tol;
-  else if (c >= b - toms748_abs(b) * tol)
-    c = b - toms748_abs(a) * tol;
-  const double fc = TOMS748_EVAL(c, args);
-  if (fc == 0) {
-    s->a = c; s->fa = 0; s->d = 0; s->fd = 0;
-  } else if (s->fa * fc < 0) {
-    s->d = b; s->fd = s->fb; s->b = c; s->fb = fc;
-  } else {
-    s->d = a; s->fd = s->fa; s->a = c; s->fa = fc;
-  }
-}
 
 /* toms748.py:53-57 */
 TOMS748_FN double toms748_safe_div(double num, double denom, double r) {
@@ -105,9 +89,38 @@ TOMS748_FN int toms748_prof(double fa, double fb, double fd, double fe) {
          toms748_abs(fb - fe) < min_diff || toms748_abs(fd - fe) < min_diff;
 }
 
+#endif /* SDM_TOMS748_H */
+
+/* ---- the part that depends on the function: once per inclusion ------------------------------ */
+#ifndef TOMS748_NAME
+#define TOMS748_NAME(name) name
+#endif
+
+/* toms748.py:24-49 */
+TOMS748_FN void TOMS748_NAME(toms748_bracket)(const TOMS748_ARGS *args, toms748_state *s,
+                                              double c) {
+  const double tol = TOMS748_EPS * 2;
+  double a = s->a, b = s->b;
+  if ((b - a) < 2 * tol * a)
+    c = a + (b - a) / 2;
+  else if (c <= a + toms748_abs(a) * tol)
+    c = a + toms748_abs(a) * tol;
+  else if (c >= b - toms748_abs(b) * tol)
+    c = b - toms748_abs(a) * tol;
+  const double fc = TOMS748_EVAL(c, args);
+  if (fc == 0) {
+    s->a = c; s->fa = 0; s->d = 0; s->fd = 0;
+  } else if (s->fa * fc < 0) {
+    s->d = b; s->fd = s->fb; s->b = c; s->fb = fc;
+  } else {
+    s->d = a; s->fd = s->fa; s->a = c; s->fa = fc;
+  }
+}
+
 /* toms748.py:115-217; *iters: the reference's second return value */
-TOMS748_FN double toms748_solve(const TOMS748_ARGS *args, double ax, double bx, double fax,
-                                double fbx, double rtol, int max_iter, int *iters) {
+TOMS748_FN double TOMS748_NAME(toms748_solve)(const TOMS748_ARGS *args, double ax, double bx,
+                                              double fax, double fbx, double rtol, int max_iter,
+                                              int *iters) {
   int count = max_iter;
   const double mu = 0.5;
   toms748_state s;
@@ -131,13 +144,13 @@ TOMS748_FN double toms748_solve(const TOMS748_ARGS *args, double ax, double bx, 
   double c;
   /* (fa != 0 here) */
   c = toms748_secant(s.a, s.b, s.fa, s.fb);
-  toms748_bracket(args, &s, c);
+  TOMS748_NAME(toms748_bracket)(args, &s, c);
   count -= 1;
   if (count > 0 && s.fa != 0 && !toms748_tol_check(s.a, s.b, rtol)) {
     c = toms748_quadratic(s.a, s.b, s.d, s.fa, s.fb, s.fd, 2);
     e = s.d;
     fe = s.fd;
-    toms748_bracket(args, &s, c);
+    TOMS748_NAME(toms748_bracket)(args, &s, c);
     count -= 1;
   }
   /* (each pass that does not break ends with count -= 1 or with a bracket at least halved: the
@@ -151,7 +164,7 @@ TOMS748_FN double toms748_solve(const TOMS748_ARGS *args, double ax, double bx, 
       c = toms748_cubic(s.a, s.b, s.d, e, s.fa, s.fb, s.fd, fe);
     e = s.d;
     fe = s.fd;
-    toms748_bracket(args, &s, c);
+    TOMS748_NAME(toms748_bracket)(args, &s, c);
     if (count == 1 || s.fa == 0 || toms748_tol_check(s.a, s.b, rtol)) {
       count -= 1;
       break;
@@ -160,7 +173,7 @@ TOMS748_FN double toms748_solve(const TOMS748_ARGS *args, double ax, double bx, 
       c = toms748_quadratic(s.a, s.b, s.d, s.fa, s.fb, s.fd, 3);
     else
       c = toms748_cubic(s.a, s.b, s.d, e, s.fa, s.fb, s.fd, fe);
-    toms748_bracket(args, &s, c);
+    TOMS748_NAME(toms748_bracket)(args, &s, c);
     if (count == 1 || s.fa == 0 || toms748_tol_check(s.a, s.b, rtol)) {
       count -= 1;
       break;
@@ -175,7 +188,7 @@ TOMS748_FN double toms748_solve(const TOMS748_ARGS *args, double ax, double bx, 
     if (toms748_abs(c - u) > (s.b - s.a) / 2) c = s.a + (s.b - s.a) / 2;
     e = s.d;
     fe = s.fd;
-    toms748_bracket(args, &s, c);
+    TOMS748_NAME(toms748_bracket)(args, &s, c);
     if (count == 1 || s.fa == 0 || toms748_tol_check(s.a, s.b, rtol)) {
       count -= 1;
       break;
@@ -183,7 +196,7 @@ TOMS748_FN double toms748_solve(const TOMS748_ARGS *args, double ax, double bx, 
     if ((s.b - s.a) < mu * (b0 - a0)) continue;
     e = s.d;
     fe = s.fd;
-    toms748_bracket(args, &s, s.a + (s.b - s.a) / 2);
+    TOMS748_NAME(toms748_bracket)(args, &s, s.a + (s.b - s.a) / 2);
     count -= 1;
   }
   *iters = max_iter - count;
@@ -192,4 +205,4 @@ TOMS748_FN double toms748_solve(const TOMS748_ARGS *args, double ax, double bx, 
   return (s.a + s.b) / 2;
 }
 
-#endif /* SDM_TOMS748_H */
+#undef TOMS748_NAME

@@ -35,6 +35,8 @@ class Engine:
     seeding_library = None
     # likewise include/sdm_relaxed_velocity.h
     relaxed_velocity_library = None
+    # likewise include/sdm_initialisation.h
+    initialisation_library = None
     # whether the fused collision step of `library` can take the fall velocity from the
     # "relative fall momentum" row; an engine that cannot must refuse, not ignore the request
     fused_momentum_velocity = False
@@ -131,6 +133,13 @@ class Engine:
         self._before_call()
         self.relaxed_velocity_library.invoke(symbol, self.handle, args)
 
+    def call_initialisation(self, symbol, *args):
+        """a symbol of include/sdm_initialisation.h"""
+        if self.initialisation_library is None:
+            raise NotImplementedError(f"engine `{self.name}` has no initialisation library")
+        self._before_call()
+        self.initialisation_library.invoke(symbol, self.handle, args)
+
     def _before_call(self):
         pass
 
@@ -166,6 +175,7 @@ class HipEngine(Engine):
         self.chemistry_library = abi.chemistry_library()
         self.seeding_library = abi.seeding_library()
         self.relaxed_velocity_library = abi.relaxed_velocity_library()
+        self.initialisation_library = abi.initialisation_library()
         self.handle = abi.c_ptr()
         self.library.check(self.library.cdll.sdm_ctx_create(ctypes.byref(self.handle),
                                                             abi.c_int(device_index)))

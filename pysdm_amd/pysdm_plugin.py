@@ -36,6 +36,12 @@
    Rogers-Yau with the formulae's constants, or the default power series; an engine whose fused
    step lacks the law refuses by name.
 
+6. Initialisation.  `equilibrate_wet_radii(**kwargs)` has the signature of
+   PySDM.initialisation.equilibrate_wet_radii and returns an ndarray, so it replaces that import
+   in a user's script (`from pysdm_amd.pysdm_plugin import equilibrate_wet_radii`); the search per
+   super-droplet is ONE `sdm_equilibrate_wet_radii`, and `environment["T"]` / `environment["RH"]`
+   are read where the backend's storages keep them.
+
 PySDM itself is imported lazily: this module loads (and fails loudly) only where PySDM exists.
 PySDM's ParticleAttributes keeps the permutation index, `cell_start`, the sorted flag and the
 number of valid super-droplets as name-mangled members (PySDM/impl/particle_attributes.py:13-46);
@@ -46,7 +52,10 @@ import copy
 import ctypes
 import importlib
 
+import numpy as np
+
 from . import abi
+from . import initialisation as init
 from . import recipe as R
 from . import relaxed_velocity as relax
 from . import seeding as seed
@@ -446,6 +455,40 @@ class FusedRelaxedVelocity(RelaxedVelocity):
             inner.terminal_vel_attr.get()
             raise ValueError(f"Radii can be interpolated up to {cfg.gk_top} m")
         attrs.mark_updated("relative fall momentum")
+
+
+def equilibrate_wet_radii(*, r_dry, environment, kappa_times_dry_volume, f_org=None,
+                          cell_id=None, rtol=init.DEFAULT_RTOL, max_iters=init.DEFAULT_MAX_ITERS):
+    """PySDM/initialisation/equilibrate_wet_radii.py:16-25 on the library: same keywords, an
+    ndarray back.  `environment["T"]` and `environment["RH"]` are used as the storages of this
+    package's backend that they are (no `to_ndarray`); storages of another backend are copied to
+    the HIP engine.  Formulae and constants are `environment.particulator.formulae`'s.  Where the
+    reference's closing assertion fires this raises pysdm_amd.initialisation.WetRadiusError, an
+    AssertionError"""
+    T, RH = environment["T"], environment["RH"]
+    # (a Storage of this package's backend classes knows its engine: backends/storage.py)
+    engine_getter = getattr(type(T), "engine_getter", None)
+    if engine_getter is None:
+        import torch  # pylint: disable=import-outside-toplevel
+
+        from .engine import HipEngine  # pylint: disable=import-outside-toplevel
+
+        if not torch.cuda.is_available():
+            raise NotImplementedError(
+                f"equilibrate_wet_radii: environment['T'] is a {type(T).__name__} of another "
+                "backend and there is no GPU to copy it to; build the environment on "
+                "PySDM.backends.HIP (pysdm_plugin.install()) or keep PySDM's own function")
+        engine = HipEngine.get()
+        T, RH = T.to_ndarray(), RH.to_ndarray()
+    else:
+        engine, T, RH = engine_getter(), T.data, RH.data
+    r_wet = init.equilibrate_wet_radii(
+        engine, environment.particulator.formulae, r_dry=np.asarray(r_dry, dtype=float),
+        kappa_times_dry_volume=np.asarray(kappa_times_dry_volume, dtype=float), T=T, RH=RH,
+        f_org=None if f_org is None else np.asarray(f_org, dtype=float),
+        cell_id=None if cell_id is None else np.asarray(cell_id, dtype=np.int64),
+        rtol=rtol, max_iters=max_iters)
+    return engine.download(r_wet)
 
 
 def fuse(dynamic):
