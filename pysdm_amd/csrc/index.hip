@@ -918,6 +918,194 @@ k_bin_sort(uint32_t *__restrict__ events, int32_t *__restrict__ toff, int32_t *_
                      s_off, inc, tab, dev_off, aff);
 }
 
+// ---- SDM_REC_CHAIN: the bin's positions as records in LDS, one of 32 bytes per position:
+//   words 0..4 the inline hit slots (-1: free), 5 the head of the overflow list (-1: none),
+//   6 the place of the position's own event in the sorted array (-1: it has none), 7 its id
+// so everything that is asked about a position comes with two 128-bit reads, where the eight rows
+// of BIN_POS words this replaces cost up to eight 4-byte reads, each from another row.
+// A record is two 16-byte chunks.  In the epilogue a thread owns the positions 4 * tid .. + 3, so
+// the 16 lanes that one 128-bit read serves together stand 128 bytes apart and would meet on 2 of
+// the 16 chunk columns of a 256-byte bank row (8-way); with bits 3..5 of the position folded into
+// the chunk number they take 16 different columns (lanes l and l + 1 differ in bit 3 of the chunk
+// number already; every group of lanes {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31}, .. holds each
+// value of (l >> 1) & 7 twice, once with l even).  The fold may exchange a record's two chunks:
+// both are only ever addressed through chain_rec_chunk.
+__device__ __forceinline__ int chain_rec_chunk(int q) {  // chunk of words 0..3; words 4..7: ^ 1
+  return (2 * q) ^ ((q >> 3) & 7);
+}
+// (lo = {slot0..slot3}, hi = {slot4, head, loc, id})
+#define CHAIN_REC_LOAD(lds, q, lo, hi)                                 \
+  const sort_v4i lo = ((const sort_v4i *)(lds))[chain_rec_chunk(q)],   \
+                 hi = ((const sort_v4i *)(lds))[chain_rec_chunk(q) ^ 1]
+// the smallest hit on the record's position with index > e (INT32_MAX: none)
+__device__ __forceinline__ int32_t chain_hit_above(sort_v4i lo, sort_v4i hi, const int32_t *links,
+                                                   int32_t e) {
+  int32_t up = INT32_MAX;
+  if (lo.x > e && lo.x < up) up = lo.x;
+  if (lo.y > e && lo.y < up) up = lo.y;
+  if (lo.z > e && lo.z < up) up = lo.z;
+  if (lo.w > e && lo.w < up) up = lo.w;
+  if (hi.x > e && hi.x < up) up = hi.x;
+  for (int32_t t = hi.y; t >= 0; t = links[t])
+    if (t > e && t < up) up = t;
+  return up;
+}
+// F(q, e) (shuffle_device.h): what the content of position p (own event at `loc`, -1: none) is
+// once all events above e have been applied, as a successor word; up: chain_hit_above(.., e)
+__device__ __forceinline__ uint32_t chain_value_after(int32_t loc, int32_t id, int32_t up,
+                                                      int32_t p, int32_t e) {
+  const int32_t own = (loc >= 0 && p > e) ? p : INT32_MAX;
+  if (up == INT32_MAX && own == INT32_MAX) return chain_word(0, id);
+  return own <= up ? chain_word(CHAIN_S, loc) : chain_word(CHAIN_T, up);
+}
+
+// the body of k_bin_build2<SDM_REC_CHAIN> from the point where the length is known.
+// At the end a thread owns the four consecutive positions base + 4 * tid .. + 3, so that first and
+// tsucc leave as one 16-byte store each (store16<BUILD_STORE>, shuffle_build.h).  Only a group that
+// lies below `length` as a whole goes that way; the one group that `length` cuts is finished word
+// by word, so nothing beyond `length` is written and neither `first` nor the tsucc carve needs
+// padding for it.
+__device__ __forceinline__ void
+bin_build_chain(int32_t *__restrict__ lds, uint32_t *__restrict__ first,
+                uint32_t *__restrict__ tsucc, const uint32_t *__restrict__ events,
+                const int32_t *__restrict__ toff, int n_bins, int n_tiles, int ev_tile,
+                const int64_t *__restrict__ idx0, int64_t length, int64_t base,
+                const int32_t *loc, int32_t *links, uint32_t *ssucc) {
+  static_assert(BIN_POS == 4 * BIN_THREADS, "a thread owns four consecutive positions");
+  constexpr int SLOTS = 5;
+  const int bin = blockIdx.x;
+  // (the order of the requests, `tpt`, RUN_AHEAD: as in the kernel below)
+  const int tpt = n_tiles >= BIN_THREADS ? 1 : BIN_THREADS / n_tiles;
+  const int sub = threadIdx.x % tpt, t_step = BIN_THREADS / tpt;
+  const int t_first = threadIdx.x / tpt;
+  int a_first = 0, b_first = 0;
+  if (t_first < n_tiles) {
+    const int32_t *row = toff + (int64_t)t_first * (n_bins + 1) + bin;
+    a_first = row[0];
+    b_first = row[1];
+  }
+  // (16 bytes per store, all 128 KB: the loc and id words are written again below)
+  for (int c = threadIdx.x; c < 2 * BIN_POS; c += BIN_THREADS)
+    ((sort_v4i *)lds)[c] = (sort_v4i){-1, -1, -1, -1};
+  constexpr int RUN_AHEAD = 8;
+  uint32_t ev0[RUN_AHEAD];
+  {
+    const uint32_t *run = events + (int64_t)t_first * ev_tile;
+#pragma unroll
+    for (int k = 0; k < RUN_AHEAD; ++k) {
+      const int x = a_first + sub + k * tpt;
+      ev0[k] = x < b_first ? run[x] : EV_NONE;  // (b_first = 0 beyond the last tile)
+    }
+  }
+  // what the records need from memory besides the hits, requested now, used after the placing.
+  // A thread takes the positions tid + k * BIN_THREADS here: four consecutive ones (two 16-byte
+  // loads of idx0, one of loc) made this phase 0.6 us longer (profiles/README.md, round 8)
+  int32_t id_v[4], loc_v[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int64_t p = base + threadIdx.x + k * BIN_THREADS;
+    id_v[k] = p < length ? (int32_t)idx0[p] : 0;
+    loc_v[k] = p < length ? loc[p] : -1;
+  }
+  BIN_MARK(9);
+  // LDS only: __syncthreads() would also wait for the global loads requested above
+  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  BIN_MARK(10);
+  // hits on this bin's positions: the first SLOTS inline (claimed by compare-and-swap), rest listed
+  auto place = [&](int2 e) {
+    const int q = e.y - (int)base;
+    const int c = chain_rec_chunk(q);
+    bool placed = false;
+#pragma unroll
+    for (int k = 0; k < SLOTS; ++k)
+      if (!placed) placed = atomicCAS(&lds[4 * (k < 4 ? c : c ^ 1) + (k & 3)], -1, e.x) == -1;
+    if (!placed) links[e.x] = atomicExch(&lds[4 * (c ^ 1) + 1], e.x);  // (-1 terminated)
+  };
+  for (int t = t_first; t < n_tiles; t += t_step) {
+    int a = a_first, b = b_first;
+    if (t != t_first) {
+      const int32_t *row = toff + (int64_t)t * (n_bins + 1) + bin;
+      a = row[0];
+      b = row[1];
+    }
+    const uint32_t *run = events + (int64_t)t * ev_tile;  // (tile-major: the tile's own segment)
+    const int32_t tile_base = t * ev_tile;
+    uint32_t ev[RUN_AHEAD];
+#pragma unroll
+    for (int k = 0; k < RUN_AHEAD; ++k) {
+      const int x = a + sub + k * tpt;
+      ev[k] = t == t_first ? ev0[k] : (x < b ? run[x] : EV_NONE);
+    }
+#pragma unroll
+    for (int k = 0; k < RUN_AHEAD; ++k)
+      if (ev[k] != EV_NONE) place(ev_unpack(ev[k], tile_base, (int32_t)base));
+    for (int x = a + sub + RUN_AHEAD * tpt; x < b; x += tpt)
+      place(ev_unpack(run[x], tile_base, (int32_t)base));
+  }
+  // (the loads requested at the kernel's start have long arrived)
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    *(int2 *)&lds[4 * (chain_rec_chunk(threadIdx.x + k * BIN_THREADS) ^ 1) + 2] =
+        make_int2(loc_v[k], id_v[k]);
+  __syncthreads();
+  BIN_MARK(11);
+  // everything that touches a position of this bin is in LDS now - its own event and the events
+  // that hit it (inline slots, the overflow list this workgroup has just built).
+  // The S word of every event that hits this bin, written where the event was read: the same runs
+  // of the tile-sorted array, the same threads.  Plain 4-byte stores: a run starts at any word
+  auto s_word = [&](int2 e) -> uint32_t {
+    CHAIN_REC_LOAD(lds, e.y - (int)base, lo, hi);
+    return chain_value_after(hi.z, hi.w, chain_hit_above(lo, hi, links, e.x), e.y, e.x);
+  };
+  for (int t = t_first; t < n_tiles; t += t_step) {
+    int a = a_first, b = b_first;
+    if (t != t_first) {
+      const int32_t *row = toff + (int64_t)t * (n_bins + 1) + bin;
+      a = row[0];
+      b = row[1];
+    }
+    const uint32_t *run = events + (int64_t)t * ev_tile;
+    const int32_t tile_base = t * ev_tile;
+    uint32_t *out = ssucc + (int64_t)t * ev_tile;
+    int x = a + sub;
+    if (t == t_first) {  // from the registers of the placing pass
+#pragma unroll
+      for (int k = 0; k < RUN_AHEAD; ++k) {
+        if (ev0[k] != EV_NONE) out[x] = s_word(ev_unpack(ev0[k], tile_base, (int32_t)base));
+        x += tpt;
+      }
+    }
+    for (; x < b; x += tpt) out[x] = s_word(ev_unpack(run[x], tile_base, (int32_t)base));
+  }
+  BIN_MARK(13);
+  // first[p] = F(q, -1); tsucc[p]: the hit above the position's own event, else its id.  Both
+  // thresholds from one read of the record
+  const int q0 = 4 * (int)threadIdx.x;
+  const int64_t p0 = base + q0;
+  const bool whole = p0 + 4 <= length;
+  uint32_t f[4], s[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int32_t p = (int32_t)p0 + k;
+    CHAIN_REC_LOAD(lds, q0 + k, lo, hi);
+    const int32_t up = chain_hit_above(lo, hi, links, p);
+    f[k] = chain_value_after(hi.z, hi.w, chain_hit_above(lo, hi, links, -1), p, -1);
+    s[k] = up == INT32_MAX ? chain_word(0, hi.w) : chain_word(CHAIN_T, up);
+  }
+  if (whole) {
+    store16<BUILD_STORE>(first, p0, (sort_v4i){(int32_t)f[0], (int32_t)f[1], (int32_t)f[2], (int32_t)f[3]});
+    store16<BUILD_STORE>(tsucc, p0, (sort_v4i){(int32_t)s[0], (int32_t)s[1], (int32_t)s[2], (int32_t)s[3]});
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (p0 + k < length) {
+        first[p0 + k] = f[k];
+        tsucc[p0 + k] = s[k];
+      }
+  }
+  BIN_MARK(12);
+}
+
 template <int FMT>
 __global__ void __launch_bounds__(BIN_THREADS)
 k_bin_build2(void *__restrict__ rec_out, int32_t *__restrict__ ovf_head,
@@ -926,15 +1114,12 @@ k_bin_build2(void *__restrict__ rec_out, int32_t *__restrict__ ovf_head,
              int n_tiles, int ev_tile, const int64_t *__restrict__ idx0,
              const int64_t *__restrict__ p_length, int64_t length_arg, BuildPrologue P) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  // (SDM_REC_CHAIN: five - a position with more hits than inline slots sends every thread that
-  // asks about it through a list in global memory, and with four slots nearly every wavefront
-  // holds such a position: 0.37 % of the positions, 0.06 % with five)
-  constexpr int SLOTS = FMT == SDM_REC_CHAIN ? 5 : FMT == SDM_REC_P21 ? 4 : (FMT == SDM_REC_P24 ? 3 : 2);
+  // (SDM_REC_CHAIN, bin_build_chain above: five - a position with more hits than inline slots sends
+  // every thread that asks about it through a list in global memory, and with four slots nearly
+  // every wavefront holds such a position: 0.37 % of the positions, 0.06 % with five)
+  constexpr int SLOTS = FMT == SDM_REC_P21 ? 4 : (FMT == SDM_REC_P24 ? 3 : 2);
   int32_t *slot = (int32_t *)smem;  // SLOTS x BIN_POS, then BIN_POS list heads
   int32_t *head = slot + SLOTS * BIN_POS;
-  // SDM_REC_CHAIN: id / place of its own event in the sorted array (-1: it has none) of every
-  // position of the bin
-  int32_t *id_l = head + BIN_POS, *loc_l = id_l + BIN_POS;
   // P.compact.fctl: the events were sorted ahead, by the pair kernel of the previous sub-step, for
   // the length that sub-step began with.  If a super-droplet died in it (rare), the compaction
   // runs here, every workgroup sorts its tile again for the new length (n_tiles == n_bins on this
@@ -960,6 +1145,13 @@ k_bin_build2(void *__restrict__ rec_out, int32_t *__restrict__ ovf_head,
   const int64_t base = (int64_t)blockIdx.x * BIN_POS;
   if (base >= length) return;
   BIN_MARK(8);
+  if (FMT == SDM_REC_CHAIN) {
+    // (first = the record buffer, tsucc = ovf_head; the overflow links have scratch of their own:
+    // ovf_next is the ssucc table here)
+    bin_build_chain((int32_t *)smem, (uint32_t *)rec_out, (uint32_t *)ovf_head, events, toff,
+                    n_bins, n_tiles, ev_tile, idx0, length, base, P.loc, P.chain_links, P.ssucc);
+    return;
+  }
   const int bin = blockIdx.x;
   constexpr int PER_POS = BIN_POS / BIN_THREADS;
   // this bin's run in every tile's segment: `tpt` threads share a tile (4 at 2^20
@@ -982,8 +1174,8 @@ k_bin_build2(void *__restrict__ rec_out, int32_t *__restrict__ ovf_head,
   for (int q = threadIdx.x; q < (SLOTS + 1) * BIN_POS / 4; q += BIN_THREADS)
     ((int4 *)slot)[q] = make_int4(-1, -1, -1, -1);
   constexpr int RUN_AHEAD = 8;
-  // (the first RUN_AHEAD events of the thread's FIRST tile - at 2^20 positions its only one - stay
-  // in registers: the S pass below needs the same events again)
+  // (bin_build_chain keeps the first RUN_AHEAD events of the thread's FIRST tile - at 2^20
+  // positions its only one - in registers: its S pass needs the same events again)
   // (packed: a word each, unpacked with the tile's and this bin's base where they are used)
   uint32_t ev0[RUN_AHEAD];
   {
@@ -996,13 +1188,12 @@ k_bin_build2(void *__restrict__ rec_out, int32_t *__restrict__ ovf_head,
   }
   // what the records need from memory besides the hits, requested now, used at the end
   int64_t id_v[PER_POS];
-  int32_t j_v[PER_POS], loc_v[PER_POS];
+  int32_t j_v[PER_POS];
 #pragma unroll
   for (int k = 0; k < PER_POS; ++k) {
     const int64_t p = base + threadIdx.x + k * BIN_THREADS;
     id_v[k] = p < length ? idx0[p] : 0;
-    j_v[k] = (FMT != SDM_REC_CHAIN && p < length) ? jarr[p] : -1;
-    loc_v[k] = (FMT == SDM_REC_CHAIN && p < length) ? P.loc[p] : -1;
+    j_v[k] = p < length ? jarr[p] : -1;
   }
   BIN_MARK(9);
   // LDS only: __syncthreads() would also wait for the global loads requested above
@@ -1015,10 +1206,8 @@ k_bin_build2(void *__restrict__ rec_out, int32_t *__restrict__ ovf_head,
 #pragma unroll
     for (int k = 0; k < SLOTS; ++k)
       if (!placed) placed = atomicCAS(&slot[k * BIN_POS + q], -1, e.x) == -1;
-    // (-1 terminated, built entirely here; SDM_REC_CHAIN keeps the links in scratch of their own:
-    // ovf_next is its ssucc table)
-    if (!placed)
-      (FMT == SDM_REC_CHAIN ? P.chain_links : ovf_next)[e.x] = atomicExch(&head[q], e.x);
+    // (-1 terminated, built entirely here)
+    if (!placed) ovf_next[e.x] = atomicExch(&head[q], e.x);
   };
   for (int t = t_first; t < n_tiles; t += t_step) {
     int a = a_first, b = b_first;
@@ -1041,70 +1230,8 @@ k_bin_build2(void *__restrict__ rec_out, int32_t *__restrict__ ovf_head,
     for (int x = a + sub + RUN_AHEAD * tpt; x < b; x += tpt)
       place(ev_unpack(run[x], tile_base, (int32_t)base));
   }
-  if (FMT == SDM_REC_CHAIN) {
-    // (the loads requested at the kernel's start have long arrived)
-#pragma unroll
-    for (int k = 0; k < PER_POS; ++k) {
-      const int q = threadIdx.x + k * BIN_THREADS;
-      id_l[q] = (int32_t)id_v[k];
-      loc_l[q] = loc_v[k];
-    }
-  }
   __syncthreads();
   BIN_MARK(11);
-  // SDM_REC_CHAIN (shuffle_device.h): everything that touches a position of this bin is in LDS now -
-  // its own event (loc_l >= 0: it has one) and the events that hit it (inline slots, the overflow
-  // list this workgroup has just built).  F(q, e): what the content of position q is once all
-  // events above e have been applied, as a successor word
-  int32_t *links = P.chain_links;
-  auto hit_above = [&](int q, int32_t e) -> int32_t {  // smallest hit on q with index > e
-    int32_t best = INT32_MAX;
-#pragma unroll
-    for (int k = 0; k < SLOTS; ++k) {
-      const int32_t v = slot[k * BIN_POS + q];
-      if (v > e && v < best) best = v;
-    }
-    for (int32_t t = head[q]; t >= 0; t = links[t])
-      if (t > e && t < best) best = t;
-    return best;
-  };
-  auto value_after = [&](int q, int32_t e) -> uint32_t {
-    const int32_t up = hit_above(q, e);
-    const int32_t pi = (int32_t)base + q;
-    const int32_t own = (loc_l[q] >= 0 && pi > e) ? pi : INT32_MAX;
-    if (up == INT32_MAX && own == INT32_MAX) return chain_word(0, id_l[q]);
-    return own <= up ? chain_word(CHAIN_S, loc_l[q]) : chain_word(CHAIN_T, up);
-  };
-  if (FMT == SDM_REC_CHAIN) {
-    // the S word of every event that hits this bin, written where the event was read: the same
-    // runs of the tile-sorted array, the same threads
-    for (int t = t_first; t < n_tiles; t += t_step) {
-      int a = a_first, b = b_first;
-      if (t != t_first) {
-        const int32_t *row = toff + (int64_t)t * (n_bins + 1) + bin;
-        a = row[0];
-        b = row[1];
-      }
-      const uint32_t *run = events + (int64_t)t * ev_tile;
-      const int32_t tile_base = t * ev_tile;
-      uint32_t *out = P.ssucc + (int64_t)t * ev_tile;
-      int x = a + sub;
-      if (t == t_first) {  // from the registers of the placing pass
-#pragma unroll
-        for (int k = 0; k < RUN_AHEAD; ++k) {
-          if (ev0[k] != EV_NONE) {
-            const int2 e = ev_unpack(ev0[k], tile_base, (int32_t)base);
-            out[x] = value_after(e.y - (int)base, e.x);
-          }
-          x += tpt;
-        }
-      }
-      for (; x < b; x += tpt) {
-        const int2 e = ev_unpack(run[x], tile_base, (int32_t)base);
-        out[x] = value_after(e.y - (int)base, e.x);
-      }
-    }
-  }
   BIN_MARK(13);
 #pragma unroll
   for (int kq = 0; kq < PER_POS; ++kq) {
@@ -1114,12 +1241,7 @@ k_bin_build2(void *__restrict__ rec_out, int32_t *__restrict__ ovf_head,
     const int32_t h = head[q];
     const int32_t id = (int32_t)id_v[kq];
     const int32_t jp = j_v[kq];
-    if (FMT == SDM_REC_CHAIN) {
-      uint32_t *first = (uint32_t *)rec_out, *tsucc = (uint32_t *)ovf_head;
-      first[p] = value_after(q, -1);
-      const int32_t up = hit_above(q, (int32_t)p);
-      tsucc[p] = up == INT32_MAX ? chain_word(0, id) : chain_word(CHAIN_T, up);
-    } else if (FMT == SDM_REC_P21) {
+    if (FMT == SDM_REC_P21) {
       PackRec21 r;
       p21_pack(r.lo, r.hi, jp, slot[q], slot[BIN_POS + q], slot[2 * BIN_POS + q],
                slot[(SLOTS - 1) * BIN_POS + q], id, h >= 0);
@@ -1136,7 +1258,7 @@ k_bin_build2(void *__restrict__ rec_out, int32_t *__restrict__ ovf_head,
       r.val = id | (h >= 0 ? (int32_t)0x80000000 : 0);
       ((PackRec *)rec_out)[p] = r;
     }
-    if (FMT != SDM_REC_CHAIN && h >= 0) ovf_head[p] = h;
+    if (h >= 0) ovf_head[p] = h;
   }
   BIN_MARK(12);
 }

@@ -59,18 +59,30 @@ __device__ __forceinline__ int2 ev_unpack(uint32_t w, int32_t tile_base, int32_t
 #endif
 typedef int32_t sort_v4i __attribute__((ext_vector_type(4)));
 typedef uint32_t sort_v4u __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void sort_store16(void *buf, int64_t at, sort_v4i v) {
-#if SORT_STORE == 2
-  // (raw buffer store: the compiler keeps count of it like of any other store; words below 2^29)
-  const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(buf, 0, 0x7fffffff, 0x00020000);
-  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(sort_v4u, v), r, (int)(at * 4), 0,
-                                         16 /* sc1 */);
-#elif SORT_STORE == 1
-  __builtin_nontemporal_store(v, (sort_v4i *)((int32_t *)buf + at));
-#else
-  *(sort_v4i *)((int32_t *)buf + at) = v;
-#endif
+template <int POLICY>
+__device__ __forceinline__ void store16(void *buf, int64_t at, sort_v4i v) {
+  if (POLICY == 2) {
+    // (raw buffer store: the compiler keeps count of it like of any other store; words below 2^29)
+    const __amdgpu_buffer_rsrc_t r =
+        __builtin_amdgcn_make_buffer_rsrc(buf, 0, 0x7fffffff, 0x00020000);
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(sort_v4u, v), r, (int)(at * 4), 0,
+                                           16 /* sc1 */);
+  } else if (POLICY == 1) {
+    __builtin_nontemporal_store(v, (sort_v4i *)((int32_t *)buf + at));
+  } else {
+    *(sort_v4i *)((int32_t *)buf + at) = v;
+  }
 }
+__device__ __forceinline__ void sort_store16(void *buf, int64_t at, sort_v4i v) {
+  store16<SORT_STORE>(buf, at, v);
+}
+// ---- the shuffle build's 16-byte stores of `first` and `tsucc` (k_bin_build2<SDM_REC_CHAIN>,
+// index.hip): 8 MB per step at 2^20 that only the next kernel reads, from other XCDs.  The same
+// three flavours, -DBUILD_STORE=0 / 1 / 2.  `nt` is the default: 0.4 - 0.5 us per step of the Shima
+// box at 2^20 against plain, `sc1` 0.2 (profiles/README.md, round 8)
+#ifndef BUILD_STORE
+#define BUILD_STORE 1
+#endif
 // dynamic LDS of the tile sort: bin starts (n_bins + 1) and counts (n_bins), rounded up to whole
 // 16 bytes, then the tile's packed events
 __host__ __device__ constexpr int bin_sort_head_words(int n_bins) { return (2 * n_bins + 2 + 3) & ~3; }
