@@ -39,6 +39,8 @@ RELAXED_VELOCITY_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include",
 # and the initialisation path (Koehler-equilibrium wet radii)
 INITIALISATION_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include",
                                           "sdm_initialisation.h")
+# and the adiabatic-parcel path (whole ascents of ensembles of parcels)
+PARCEL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "sdm_parcel.h")
 # SDM_HIP_LIB: another build of the same library (tuning variants); still no fallback
 HIP_LIB_PATH = os.environ.get("SDM_HIP_LIB") or os.path.join(_HERE, "libsdm_hip.so")
 
@@ -158,6 +160,31 @@ class ChemistryCfg(ctypes.Structure):  # == sdm_chemistry_cfg (include/sdm_chemi
 
 class CondFormulae(ctypes.Structure):  # == sdm_cond_formulae (include/sdm_condensation_formulae.h)
     _fields_ = [("option", ctypes.c_int32 * 10), ("consts", c_f64 * 72)]
+
+
+class ParcelCfg(ctypes.Structure):  # == sdm_parcel_cfg (include/sdm_parcel.h)
+    _fields_ = [
+        ("dt", c_f64), ("g_std", c_f64), ("rtol_x", c_f64), ("rtol_thd", c_f64),
+        ("dt_min", c_f64), ("dt_max", c_f64), ("RH_rtol", c_f64),
+        ("adaptive", ctypes.c_int32), ("fuse", ctypes.c_int32), ("multiplier", ctypes.c_int32),
+        ("max_iters", ctypes.c_int32), ("n_clamp_lo", c_i64), ("n_clamp_hi", c_i64),
+        ("steps_per_launch", ctypes.c_int32), ("reserved", ctypes.c_int32),
+    ]
+
+
+PARCEL_STATE_FLOATS = ("z", "rhod", "thd", "qv", "T", "p", "RH", "qv_prev", "mass_of_dry_air")
+PARCEL_STATE_FIELDS = (*PARCEL_STATE_FLOATS, "n_substeps", "n_activating", "n_deactivating",
+                       "n_ripening", "RH_max", "steps_done", "failed_step")
+PARCEL_PROFILE_FIELDS = ("z", "rhod", "thd", "qv", "T", "p", "RH", "RH_max", "n_substeps",
+                         "n_activating", "n_deactivating", "n_ripening")
+
+
+class ParcelState(ctypes.Structure):  # == sdm_parcel_state
+    _fields_ = [(name, c_ptr) for name in PARCEL_STATE_FIELDS]
+
+
+class ParcelProfile(ctypes.Structure):  # == sdm_parcel_profile
+    _fields_ = [(name, c_ptr) for name in PARCEL_PROFILE_FIELDS]
 
 
 class RelaxedVelocityCfg(ctypes.Structure):  # == sdm_relaxed_velocity_cfg
@@ -335,6 +362,7 @@ _chemistry_library = None
 _seeding_library = None
 _relaxed_velocity_library = None
 _initialisation_library = None
+_parcel_library = None
 
 
 def hip_library():
@@ -415,6 +443,15 @@ def initialisation_library():
         _initialisation_library = Library(HIP_LIB_PATH, "the HIP kernels of pysdm_amd",
                                           header=INITIALISATION_HEADER_PATH)
     return _initialisation_library
+
+
+def parcel_library():
+    """libsdm_hip.so bound to include/sdm_parcel.h (same file, same contexts)"""
+    global _parcel_library  # pylint: disable=global-statement
+    if _parcel_library is None:
+        _parcel_library = Library(HIP_LIB_PATH, "the HIP kernels of pysdm_amd",
+                                  header=PARCEL_HEADER_PATH)
+    return _parcel_library
 
 
 def pcg64_state_inc(seed):

@@ -111,6 +111,12 @@ struct sdm_ctx {
   // displacement.hip (sharded step): precipitated masses by position, zero between uses
   double *rain_carry;
   int64_t rain_carry_len;
+  // parcel.hip: the identity permutation and the copy of the water masses a step may have to put
+  // back, `parcel_rows` entries each (grown on demand; buffers of their own, not the arena, whose
+  // contents other paths carry from call to call)
+  int64_t *parcel_identity;
+  double *parcel_backup;
+  int64_t parcel_rows;
   // device control words for fine-grained calls (int64[16]; word 6: dt_left[0] of an adaptive
   // single cell for the next sub-step, fused.hip; 8: a length; 10-11: adaptive_end; 12-15: barrier)
   int64_t *dscal;

@@ -5,7 +5,7 @@
 // Reference: PySDM/backends/impl_numba/methods/condensation_methods.py ("cm.py"), toms748.py and
 // physics_methods.py ("pm.py"), with PySDM's default formulae inlined (physics/...).  The CPU
 // checker of this file is tests/checker/condensation_checker.c.
-#include "condensation_solver.h"
+#include "parcel_solver.h"
 #include "../../include/sdm_condensation.h"
 
 #define GRID1D(n) dim3(grid_for(n)), dim3(SDM_BLOCK), 0, ctx->stream
@@ -54,7 +54,21 @@ DF double RH_eq_of(const Kc &k, double r, double T, double kp, double rd3, doubl
   return 1 + (2 * sgm / k.Rv / T / k.rho_w) / r - kp * rd3 / sdm_pow(r, k.THREE);
 }
 
-// the policy of condensation_solver.h for PySDM's default formulae
+// pm.py:53-61: what k_temperature_pressure_rh writes for one cell and the parcel kernel for a parcel
+DF void tprh_of(const Kc &k, double rhod, double thd, double qv, double &T, double &p, double &RH) {
+  T = svt_T(k, rhod, thd);
+  p = svt_p(k, rhod, T, qv);
+  RH = svt_pv(k, p, qv) / pvs_water(k, T);
+}
+// pm.py:22-33; kappa_koehler_leading_terms.py:23-25 (r_cr), trivia.py:27-28 (volume): what
+// k_critical_volume writes for one droplet and the parcel kernel for a row
+DF double critical_volume_of(const Kc &k, double kappa, double v_dry, double t) {
+  const double sgm = k.sgm_w;
+  const double r_cr = SDM_MATH_SQRT(3 * kappa * (v_dry / k.PI_4_3) / (2 * sgm / k.Rv / t / k.rho_w));
+  return k.PI_4_3 * sdm_pow(r_cr, k.THREE);
+}
+
+// the policy of condensation_solver.h (and parcel_solver.h) for PySDM's default formulae
 struct DefaultFormulae {
   using K = Kc;
   struct Extra {};  // surface_tension Constant reads no f_org, ventilation Neglect no Re
@@ -72,6 +86,19 @@ struct DefaultFormulae {
   DF static double x_of(const Kc &, double m) { return sdm_log(m); }  // water_mass_logarithm.py
   DF static double mass_of(const Kc &, double x) { return sdm_exp(x); }
   DF static bool failed(const MinArgs &) { return false; }
+  // parcel_solver.h
+  DF static double Rv(const Kc &k) { return k.Rv; }
+  DF static double Rd(const Kc &k) { return k.Rd; }
+  DF static double c_pv(const Kc &k) { return k.c_pv; }
+  DF static double lv(const Kc &k, double T) { return lv_of(k, T); }
+  DF static void tprh(const Kc &k, double rhod, double thd, double qv, double &T, double &p,
+                      double &RH) {
+    tprh_of(k, rhod, thd, qv, T, p, RH);
+  }
+  DF static double critical_volume(const Kc &k, int64_t, double kappa, double v_dry, double,
+                                   double T) {  // surface_tension Constant: no v_wet, no f_org
+    return critical_volume_of(k, kappa, v_dry, T);
+  }
 
   // minfun, cm.py:366-397
   DF static double minfun(const Kc &k, double x_new, const MinArgs &a) {
@@ -134,16 +161,22 @@ __global__ __launch_bounds__(COND_CB) void k_condensation(CondArgs<DefaultFormul
   condensation_cell<DefaultFormulae>(g);
 }
 
+// include/sdm_parcel.h with PySDM's default formulae: one workgroup per parcel, the launch's time
+// steps inside (parcel_solver.h)
+__global__ __launch_bounds__(COND_CB) void k_parcel(ParcelArgs<DefaultFormulae> a) {
+  parcel_steps<DefaultFormulae>(a);
+}
+
 // ---- ambient methods (pm.py) ---------------------------------------------------------------------
 __global__ void k_temperature_pressure_rh(const double *rhod, const double *thd, const double *qv,
                                           double *T, double *p, double *RH, int64_t n, Kc k) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const double t = svt_T(k, rhod[i], thd[i]);  // pm.py:53-61
-  const double pp = svt_p(k, rhod[i], t, qv[i]);
+  double t, pp, rh;
+  tprh_of(k, rhod[i], thd[i], qv[i], t, pp, rh);
   T[i] = t;
   p[i] = pp;
-  RH[i] = svt_pv(k, pp, qv[i]) / pvs_water(k, t);
+  RH[i] = rh;
 }
 
 __global__ void k_air_density(double *out, const double *rhod, const double *qv, int64_t n) {
@@ -162,12 +195,7 @@ __global__ void k_critical_volume(double *v_cr, const double *kappa, const doubl
                                   const double *T, const int64_t *cell, int64_t n, Kc k) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i >= n) return;
-  // pm.py:22-33; kappa_koehler_leading_terms.py:23-25 (r_cr), trivia.py:27-28 (volume)
-  const double sgm = k.sgm_w;
-  const double t = T[cell[i]];
-  const double r_cr = SDM_MATH_SQRT(3 * kappa[i] * (v_dry[i] / k.PI_4_3) /
-                                    (2 * sgm / k.Rv / t / k.rho_w));
-  v_cr[i] = k.PI_4_3 * sdm_pow(r_cr, k.THREE);
+  v_cr[i] = critical_volume_of(k, kappa[i], v_dry[i], T[cell[i]]);
 }
 
 __global__ void k_reynolds_number(double *out, const int64_t *cell_id, const double *eta,
@@ -205,6 +233,15 @@ extern "C" int sdm_condensation(
   SDM_COND_FILL_ARGS(g);
   g.k = consts_of(consts);
   hipLaunchKernelGGL(k_condensation, dim3((unsigned)n_cell), dim3(COND_CB), 0, ctx->stream, g);
+  LAUNCH_CHECK();
+  return SDM_OK;
+}
+
+int sdm_parcel_launch_default(sdm_ctx *ctx, const ParcelCall &call) {
+  ParcelArgs<DefaultFormulae> a;
+  SDM_PARCEL_FILL_ARGS(a, call);
+  a.c.k = consts_of(call.consts);
+  hipLaunchKernelGGL(k_parcel, dim3((unsigned)call.n_parcel), dim3(COND_CB), 0, ctx->stream, a);
   LAUNCH_CHECK();
   return SDM_OK;
 }

@@ -14,7 +14,7 @@
 //
 // The CPU checker of this file is tests/condensation_formulae_checker/, which compiles the same
 // condensation_formulae.h.
-#include "condensation_solver.h"
+#include "parcel_solver.h"
 #include "../../include/sdm_condensation_formulae.h"
 
 #define CF_FN __device__ __forceinline__ static
@@ -31,7 +31,30 @@ struct Kg {
   const double *air_density, *air_dynamic_viscosity;  // per cell
 };
 
-// the policy of condensation_solver.h for any combination of choices
+// pm.py:53-61: what k_temperature_pressure_rh_f writes for one cell and the parcel kernel for a
+// parcel
+DF void tprh_of(const cf_k *k, double rhod, double thd, double qv, double &T, double &p,
+                double &RH) {
+  T = cf_svt_T(k, rhod, thd);
+  p = cf_svt_p(k, rhod, T, qv);
+  RH = cf_svt_pv(k, p, qv) / cf_pvs_water(k, T);
+}
+// pm.py:22-33: what k_critical_volume_f writes for one droplet and the parcel kernel for a row
+// (f_org and v_wet are read only where the surface tension is not Constant)
+DF double critical_volume_of(const cf_k *k, double kappa, const double *f_org, double v_dry,
+                             double v_wet, double t) {
+  int fail = 0;
+  double forg = 0.0, vwet = 0.0;
+  if (CF_O(SURFACE_TENSION) != SDM_COND_SGM_CONSTANT) {
+    forg = *f_org;
+    vwet = v_wet;
+  }
+  const double sigma = cf_sigma(k, t, vwet, v_dry, forg, &fail);
+  const double r_cr = cf_r_cr(k, kappa, v_dry / CF_C(PI_4_3), t, sigma);
+  return fail ? sdm_nan() : cf_volume(k, r_cr);
+}
+
+// the policy of condensation_solver.h (and parcel_solver.h) for any combination of choices
 struct GeneralFormulae {
   using K = Kg;
   struct Extra {
@@ -52,6 +75,19 @@ struct GeneralFormulae {
   DF static double x_of(const Kg &k, double m) { return cf_x(&k.f, m); }
   DF static double mass_of(const Kg &k, double x) { return cf_mass(&k.f, x); }
   DF static bool failed(const MinArgs &a) { return a.fail != 0; }
+  // parcel_solver.h
+  DF static double Rv(const Kg &k) { return k.f.c[SDM_COND_K_RV]; }
+  DF static double Rd(const Kg &k) { return k.f.c[SDM_COND_K_RD]; }
+  DF static double c_pv(const Kg &k) { return k.f.c[SDM_COND_K_C_PV]; }
+  DF static double lv(const Kg &k, double T) { return cf_lv(&k.f, T); }
+  DF static void tprh(const Kg &k, double rhod, double thd, double qv, double &T, double &p,
+                      double &RH) {
+    tprh_of(&k.f, rhod, thd, qv, T, p, RH);
+  }
+  DF static double critical_volume(const Kg &k, int64_t row, double kappa, double v_dry,
+                                   double v_wet, double T) {
+    return critical_volume_of(&k.f, kappa, k.f_org ? k.f_org + row : nullptr, v_dry, v_wet, T);
+  }
 
   DF static Extra extra_of(const Kg &k, int64_t drop) {
     Extra e;
@@ -137,18 +173,23 @@ __global__ __launch_bounds__(COND_CB) void k_condensation_f(CondArgs<GeneralForm
   condensation_cell<GeneralFormulae>(g);
 }
 
+// include/sdm_parcel.h with a formulae descriptor: one workgroup per parcel, the launch's time
+// steps inside (parcel_solver.h)
+__global__ __launch_bounds__(COND_CB) void k_parcel_f(ParcelArgs<GeneralFormulae> a) {
+  parcel_steps<GeneralFormulae>(a);
+}
+
 // ---- ambient methods (pm.py) ---------------------------------------------------------------------
 __global__ void k_temperature_pressure_rh_f(const double *rhod, const double *thd,
                                             const double *qv, double *T, double *p, double *RH,
                                             int64_t n, cf_k kk) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const cf_k *k = &kk;
-  const double t = cf_svt_T(k, rhod[i], thd[i]);  // pm.py:53-61
-  const double pp = cf_svt_p(k, rhod[i], t, qv[i]);
+  double t, pp, rh;
+  tprh_of(&kk, rhod[i], thd[i], qv[i], t, pp, rh);
   T[i] = t;
   p[i] = pp;
-  RH[i] = cf_svt_pv(k, pp, qv[i]) / cf_pvs_water(k, t);
+  RH[i] = rh;
 }
 
 __global__ void k_critical_volume_f(double *v_cr, const double *kappa, const double *f_org,
@@ -157,17 +198,9 @@ __global__ void k_critical_volume_f(double *v_cr, const double *kappa, const dou
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i >= n) return;
   const cf_k *k = &kk;
-  // pm.py:22-33
-  const double t = T[cell[i]];
-  int fail = 0;
-  double forg = 0.0, vwet = 0.0;
-  if (CF_O(SURFACE_TENSION) != SDM_COND_SGM_CONSTANT) {
-    forg = f_org[i];
-    vwet = v_wet[i];
-  }
-  const double sigma = cf_sigma(k, t, vwet, v_dry[i], forg, &fail);
-  const double r_cr = cf_r_cr(k, kappa[i], v_dry[i] / CF_C(PI_4_3), t, sigma);
-  v_cr[i] = fail ? sdm_nan() : cf_volume(k, r_cr);
+  const bool film = CF_O(SURFACE_TENSION) != SDM_COND_SGM_CONSTANT;
+  v_cr[i] = critical_volume_of(k, kappa[i], film ? f_org + i : nullptr, v_dry[i],
+                               film ? v_wet[i] : 0.0, T[cell[i]]);
 }
 
 // the descriptor and the default path's constants as the kernels' argument; refuses codes the
@@ -210,6 +243,23 @@ extern "C" int sdm_condensation_f(
   g.k.air_density = air_density;
   g.k.air_dynamic_viscosity = air_dynamic_viscosity;
   hipLaunchKernelGGL(k_condensation_f, dim3((unsigned)n_cell), dim3(COND_CB), 0, ctx->stream, g);
+  LAUNCH_CHECK();
+  return SDM_OK;
+}
+
+int sdm_parcel_launch_general(sdm_ctx *ctx, const ParcelCall &call,
+                              const sdm_cond_formulae *formulae) {
+  ParcelArgs<GeneralFormulae> a;
+  SDM_PARCEL_FILL_ARGS(a, call);
+  ARG_TRY(formulae && formulae_of(call.consts, formulae, &a.c.k.f));
+  // (ventilation needs a fall velocity per droplet per step: it stays on the stage route)
+  ARG_TRY(formulae->option[SDM_COND_OPT_VENTILATION] == SDM_COND_VENT_NEGLECT);
+  ARG_TRY(formulae->option[SDM_COND_OPT_SURFACE_TENSION] == SDM_COND_SGM_CONSTANT || call.f_org);
+  a.c.k.f_org = call.f_org;
+  a.c.k.reynolds_number = nullptr;
+  a.c.k.vdry = call.vdry;
+  a.c.k.air_density = a.c.k.air_dynamic_viscosity = nullptr;
+  hipLaunchKernelGGL(k_parcel_f, dim3((unsigned)call.n_parcel), dim3(COND_CB), 0, ctx->stream, a);
   LAUNCH_CHECK();
   return SDM_OK;
 }

@@ -506,9 +506,9 @@ DF int64_t floordiv(int64_t a, int64_t b) {
   return (a % b != 0 && ((a < 0) != (b < 0))) ? q - 1 : q;
 }
 
-// the body of the kernel of either instantiation (_condensation, cm.py:126-176)
+// the LDS of one workgroup's CellSolver (one set per kernel: declared where this is inlined)
 template <class P>
-DF void condensation_cell(const CondArgs<P> &g) {
+DF void attach_lds(CellSolver<P> &cs) {
   __shared__ double col[COND_CH];
   __shared__ int s_badq;
   __shared__ double s_sum, s_probe;
@@ -519,11 +519,6 @@ DF void condensation_cell(const CondArgs<P> &g) {
     __shared__ double s_stage[P::STAGE > 0 ? P::STAGE : 1];
     stage = s_stage;
   }
-  const int64_t cell = g.cell_order[blockIdx.x];
-  if (cell < 0 || cell >= g.n_cell) return;
-  const int64_t start = g.cell_start[cell], end = g.cell_start[cell + 1];
-  if (start < 0 || end > g.n_sd || end <= start) return;  // empty cells are skipped
-  CellSolver<P> cs{g, g.idx + start, end - start, cell, (int)threadIdx.x};
   cs.col = col;
   cs.stage = stage;
   cs.s_badq = &s_badq;
@@ -531,18 +526,26 @@ DF void condensation_cell(const CondArgs<P> &g) {
   cs.s_probe = &s_probe;
   cs.s_fail = &s_fail;
   cs.s_cnt = s_cnt;
-  cs.init();
+}
 
-  const double thd = g.thd[cell], qv = g.qv[cell], rhod = g.rhod[cell];
-  const double dthd_dt = (g.pthd[cell] - thd) / g.timestep;
-  const double dqv_dt = (g.pqv[cell] - qv) / g.timestep;
-  const double drhod_dt = (g.prhod[cell] - rhod) / g.timestep;
-  const double m_d = (g.prhod[cell] + rhod) / 2 * g.dv;
-  __syncthreads();  // every lane has read pthd / pqv before lane 0 writes them
+struct SolveOut {
+  StepOut o;
+  int64_t n;  // the sub-step count used
+  int ran;    // the real step ran (the register-cached masses are the new ones)
+};
 
-  // solve, cm.py:636-698 (adapt_substeps :190-227, step_fake :231-238)
+// the solve proper (solve, cm.py:636-698; adapt_substeps :190-227, step_fake :231-238) with the
+// cell's scalars as arguments: k_condensation(_f) read them from CondArgs (condensation_cell), the
+// parcel kernels keep them in registers from step to step (parcel_solver.h).  `n`: the previous
+// sub-step count.  The caller has run cs.init() and calls cs.write_back() if `ran`.
+template <class P>
+DF SolveOut solve_cell(CellSolver<P> &cs, const CondArgs<P> &g, double thd, double qv,
+                       double rhod, double prhod, double pthd, double pqv, double dv, int64_t n) {
+  const double dthd_dt = (pthd - thd) / g.timestep;
+  const double dqv_dt = (pqv - qv) / g.timestep;
+  const double drhod_dt = (prhod - rhod) / g.timestep;
+  const double m_d = (prhod + rhod) / 2 * dv;
   int ok = 1;
-  int64_t n = g.n_substeps[cell];
   if (g.adaptive) {
     const int64_t mult = g.multiplier;
     const int64_t fd = floordiv(n, mult);
@@ -575,22 +578,42 @@ DF void condensation_cell(const CondArgs<P> &g) {
     }
     if (ok) n = g.n_max < n ? g.n_max : n;
   }
-  StepOut o;
-  if (ok) {
-    o = cs.step_impl(thd, qv, rhod, dthd_dt, dqv_dt, drhod_dt, m_d, g.timestep, n, false);
-    cs.write_back();
-  } else {
-    o = StepOut{qv, thd, -1, -1, -1, -1, 0};
-  }
+  SolveOut s;
+  s.n = n;
+  s.ran = ok;
+  if (ok) s.o = cs.step_impl(thd, qv, rhod, dthd_dt, dqv_dt, drhod_dt, m_d, g.timestep, n, false);
+  else s.o = StepOut{qv, thd, -1, -1, -1, -1, 0};
+  return s;
+}
+
+// the body of the kernel of either instantiation (_condensation, cm.py:126-176): the cell's
+// scalars from CondArgs, the solve proper, the cell's results
+template <class P>
+DF void condensation_cell(const CondArgs<P> &g) {
+  const int64_t cell = g.cell_order[blockIdx.x];
+  if (cell < 0 || cell >= g.n_cell) return;
+  const int64_t start = g.cell_start[cell], end = g.cell_start[cell + 1];
+  if (start < 0 || end > g.n_sd || end <= start) return;  // empty cells are skipped
+  CellSolver<P> cs{g, g.idx + start, end - start, cell, (int)threadIdx.x};
+  attach_lds<P>(cs);
+  cs.init();
+
+  const double thd = g.thd[cell], qv = g.qv[cell], rhod = g.rhod[cell];
+  const double prhod = g.prhod[cell], pthd = g.pthd[cell], pqv = g.pqv[cell];
+  __syncthreads();  // every lane has read pthd / pqv before lane 0 writes them
+
+  const SolveOut s = solve_cell<P>(cs, g, thd, qv, rhod, prhod, pthd, pqv, g.dv,
+                                   g.n_substeps[cell]);
+  if (s.ran) cs.write_back();
   if (threadIdx.x == 0) {
-    g.success[cell] = (uint8_t)(o.success != 0);
-    g.pqv[cell] = o.qv;
-    g.pthd[cell] = o.thd;
-    g.n_substeps[cell] = n;
-    g.n_activating[cell] = o.n_activating;
-    g.n_deactivating[cell] = o.n_deactivating;
-    g.n_ripening[cell] = o.n_ripening;
-    g.RH_max[cell] = o.RH_max;
+    g.success[cell] = (uint8_t)(s.o.success != 0);
+    g.pqv[cell] = s.o.qv;
+    g.pthd[cell] = s.o.thd;
+    g.n_substeps[cell] = s.n;
+    g.n_activating[cell] = s.o.n_activating;
+    g.n_deactivating[cell] = s.o.n_deactivating;
+    g.n_ripening[cell] = s.o.n_ripening;
+    g.RH_max[cell] = s.o.RH_max;
   }
 }
 

@@ -125,6 +125,8 @@ extern "C" int sdm_ctx_destroy(sdm_ctx *ctx) {
   if (ctx->dead_pos) (void)hipFree(ctx->dead_pos);
   if (ctx->dead_ctr) (void)hipFree(ctx->dead_ctr);
   if (ctx->rain_carry) (void)hipFree(ctx->rain_carry);
+  if (ctx->parcel_identity) (void)hipFree(ctx->parcel_identity);
+  if (ctx->parcel_backup) (void)hipFree(ctx->parcel_backup);
   if (ctx->graph_exec) (void)hipGraphExecDestroy((hipGraphExec_t)ctx->graph_exec);
   free(ctx->graph_key);
   if (ctx->gwords) (void)hipFree(ctx->gwords);

@@ -1,0 +1,100 @@
+// parcel.hip -- the entry point of include/sdm_parcel.h: argument checks, the two buffers the
+// kernels need beyond the caller's arrays, and the chunking of a call into launches.  The kernels
+// are the instantiations of parcel_solver.h (where their design is described) next to those of the
+// condensation solver: k_parcel in condensation.hip (PySDM's default formulae), k_parcel_f in
+// condensation_formulae.hip (a descriptor); this file reaches both through their launchers.
+//
+// A call of n_steps enqueues ceil(n_steps / steps_per_launch) launches back to back on the
+// context's stream, without synchronising between them: one launch stays short on a shared card,
+// and nothing but the stream orders them (launch k + 1 reads the state arrays launch k wrote).
+#include <vector>
+
+#include "parcel_solver.h"
+
+namespace {
+
+// the identity permutation (written once per growth) and the backup column, n_sd entries each
+int reserve_rows(sdm_ctx *ctx, int64_t n_sd) {
+  if (n_sd <= ctx->parcel_rows) return SDM_OK;
+  HIP_TRY(hipStreamSynchronize(ctx->stream));  // earlier launches may still read the old ones
+  if (ctx->parcel_identity) HIP_TRY(hipFree(ctx->parcel_identity));
+  if (ctx->parcel_backup) HIP_TRY(hipFree(ctx->parcel_backup));
+  ctx->parcel_identity = nullptr;
+  ctx->parcel_backup = nullptr;
+  ctx->parcel_rows = 0;
+  const int64_t want = n_sd + n_sd / 4 + 1024;
+  if (hipMalloc((void **)&ctx->parcel_identity, (size_t)want * sizeof(int64_t)) != hipSuccess ||
+      hipMalloc((void **)&ctx->parcel_backup, (size_t)want * sizeof(double)) != hipSuccess) {
+    sdm_set_error("sdm_parcel_run: hipMalloc of 2 x %lld words failed", (long long)want);
+    return SDM_E_NOMEM;
+  }
+  ctx->parcel_rows = want;
+  return sdm_identity_index(ctx, ctx->parcel_identity, want);
+}
+
+}  // namespace
+
+extern "C" int sdm_parcel_run(sdm_ctx *ctx, const sdm_parcel_cfg *cfg, int64_t n_steps,
+                              int64_t n_parcel, int64_t n_sd, const int64_t *parcel_start,
+                              double *water_mass, const int64_t *multiplicity,
+                              const double *vdry, const double *kappa, const double *f_org,
+                              double *v_cr, const sdm_parcel_state *state, const double *w_mid,
+                              const sdm_parcel_profile *profile, const double consts[34],
+                              const sdm_cond_formulae *formulae) {
+  ARG_TRY(ctx && cfg && consts && state);
+  ARG_TRY(n_steps >= 0 && n_parcel >= 0 && n_sd >= 0 && n_parcel <= 0x7fffffff);
+  ARG_TRY(cfg->multiplier >= 1 && cfg->fuse >= 0 && cfg->max_iters >= 0 && cfg->dt > 0);
+  ARG_TRY(cfg->dt_min != 0);
+  ARG_TRY(cfg->steps_per_launch >= 0);
+  if (formulae)  // (the general launcher checks the rest of the descriptor)
+    ARG_TRY(formulae->option[SDM_COND_OPT_VENTILATION] == SDM_COND_VENT_NEGLECT);
+  if (n_parcel == 0 || n_steps == 0) return SDM_OK;
+  ARG_TRY(parcel_start && water_mass && multiplicity && vdry && kappa && v_cr && w_mid);
+  ARG_TRY(state->z && state->rhod && state->thd && state->qv && state->T && state->p &&
+          state->RH && state->qv_prev && state->mass_of_dry_air && state->n_substeps &&
+          state->n_activating && state->n_deactivating && state->n_ripening && state->RH_max &&
+          state->steps_done && state->failed_step);
+  {  // every parcel has rows, and they lie within the columns: the kernels index by these words
+    std::vector<int64_t> starts((size_t)n_parcel + 1);
+    HIP_TRY(hipMemcpyAsync(starts.data(), parcel_start, starts.size() * sizeof(int64_t),
+                           hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    ARG_TRY(starts[0] >= 0 && starts[(size_t)n_parcel] <= n_sd);
+    for (int64_t c = 0; c < n_parcel; ++c)
+      if (starts[(size_t)c + 1] <= starts[(size_t)c]) {
+        sdm_set_error("sdm_parcel_run: parcel %lld has no rows", (long long)c);
+        return SDM_E_ARG;
+      }
+  }
+  const int rc = reserve_rows(ctx, n_sd);
+  if (rc != SDM_OK) return rc;
+
+  ParcelCall call;
+  call.cfg = *cfg;
+  call.n_parcel = n_parcel;
+  call.n_sd = n_sd;
+  call.parcel_start = parcel_start;
+  call.identity = ctx->parcel_identity;
+  call.multiplicity = multiplicity;
+  call.water_mass = water_mass;
+  call.v_cr = v_cr;
+  call.mass_backup = ctx->parcel_backup;
+  call.vdry = vdry;
+  call.kappa = kappa;
+  call.f_org = f_org;
+  call.w_mid = w_mid;
+  call.consts = consts;
+  call.state = *state;
+  if (profile) call.profile = *profile;
+  else memset(&call.profile, 0, sizeof(call.profile));
+  const int64_t per_launch =
+      cfg->steps_per_launch > 0 ? cfg->steps_per_launch : SDM_PARCEL_STEPS_PER_LAUNCH;
+  for (int64_t k0 = 0; k0 < n_steps; k0 += per_launch) {
+    call.k0 = k0;
+    call.k_count = n_steps - k0 < per_launch ? n_steps - k0 : per_launch;
+    const int launched = formulae ? sdm_parcel_launch_general(ctx, call, formulae)
+                                  : sdm_parcel_launch_default(ctx, call);
+    if (launched != SDM_OK) return launched;
+  }
+  return SDM_OK;
+}

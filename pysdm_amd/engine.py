@@ -37,6 +37,8 @@ class Engine:
     relaxed_velocity_library = None
     # likewise include/sdm_initialisation.h
     initialisation_library = None
+    # likewise include/sdm_parcel.h
+    parcel_library = None
     # whether the fused collision step of `library` can take the fall velocity from the
     # "relative fall momentum" row; an engine that cannot must refuse, not ignore the request
     fused_momentum_velocity = False
@@ -140,6 +142,13 @@ class Engine:
         self._before_call()
         self.initialisation_library.invoke(symbol, self.handle, args)
 
+    def call_parcel(self, symbol, *args):
+        """a symbol of include/sdm_parcel.h"""
+        if self.parcel_library is None:
+            raise NotImplementedError(f"engine `{self.name}` has no parcel library")
+        self._before_call()
+        self.parcel_library.invoke(symbol, self.handle, args)
+
     def _before_call(self):
         pass
 
@@ -176,6 +185,7 @@ class HipEngine(Engine):
         self.seeding_library = abi.seeding_library()
         self.relaxed_velocity_library = abi.relaxed_velocity_library()
         self.initialisation_library = abi.initialisation_library()
+        self.parcel_library = abi.parcel_library()
         self.handle = abi.c_ptr()
         self.library.check(self.library.cdll.sdm_ctx_create(ctypes.byref(self.handle),
                                                             abi.c_int(device_index)))

@@ -1,0 +1,446 @@
+"""The adiabatic parcel on the library (include/sdm_parcel.h): PySDM's `Parcel` environment with
+the dynamics `AmbientThermodynamics` and `Condensation`, for an ensemble of independent parcels.
+
+`ParcelRunner` holds the parcels' state (per parcel: z, rhod, thd, qv, T, p, RH, the previous qv,
+the solver's counters; per super-droplet: water mass, multiplicity, dry volume, kappa, f_org and
+the critical volume) as engine arrays and runs time steps on one of two routes:
+
+* ``route="fused"``: `sdm_parcel_run` - one library call for `n_steps` steps of all parcels, the
+  loop over the steps inside the kernel, nothing read back between the steps;
+* ``route="stages"``: the same time step written with the symbols of include/sdm_condensation.h
+  (and its `_f` forms): the advance of the parcel's variables in Python floats, then
+  `sdm_critical_volume`, `sdm_condensation` and `sdm_temperature_pressure_rh`, per parcel on
+  slices of the columns with n_cell = 1.  It is the yardstick of the fused route (the two agree
+  bit for bit) and the only route with a ventilation other than Neglect.
+
+The time step is the one include/sdm_parcel.h writes out (environments/parcel.py:101-153,
+environments/impl/moist.py:73-100, dynamics/condensation.py:95-131), with the hydrostatics
+ConstantGVapourMixingRatioAndThetaStd; the initial state follows `Parcel.register`
+(parcel.py:51-71).  Products and observers have no place here: `run` returns the profile.
+"""
+import numpy as np
+
+from . import abi
+from .condensation import (CONSTANT_NAMES, OPTION_ORDER, _option_name, check_formulae,
+                           condensation_call, critical_volume_call, is_default,
+                           temperature_pressure_rh_call)
+from .engine import FLOAT, INT
+
+HYDROSTATICS = "ConstantGVapourMixingRatioAndThetaStd"
+G_STD = 9.80665  # PySDM/physics/constants_defaults.py: g_std (scipy.constants.g)
+ROUTES = ("fused", "stages")
+_INT_FIELDS = ("n_substeps", "n_activating", "n_deactivating", "n_ripening", "steps_done",
+               "failed_step")
+_LV = OPTION_ORDER.index("latent_heat_vapourisation")
+
+
+def _address(array, dtype):
+    """the address of a contiguous engine array of `dtype` (numpy array or torch tensor): what the
+    members of ParcelState / ParcelProfile hold (the binding checks only direct arguments)"""
+    if array is None:
+        return None
+    if isinstance(array, np.ndarray):
+        if not array.flags["C_CONTIGUOUS"] or array.dtype.type is not dtype:
+            raise TypeError(f"parcel: expected a contiguous {np.dtype(dtype).name} array")
+        return array.ctypes.data
+    if not array.is_contiguous() or str(array.dtype).rsplit(".", 1)[-1] != np.dtype(dtype).name:
+        raise TypeError(f"parcel: expected a contiguous {np.dtype(dtype).name} array")
+    return array.data_ptr()
+
+
+def check_hydrostatics(formulae):
+    """the parcel's density derivative is ConstantGVapourMixingRatioAndThetaStd.drho_dz (PySDM's
+    default); a `Formulae` naming another hydrostatics is refused"""
+    value = getattr(formulae, "hydrostatics", None)
+    if value is not None and _option_name(value) != HYDROSTATICS:
+        raise NotImplementedError(f"parcel supports hydrostatics={HYDROSTATICS!r} only, "
+                                  f"not {_option_name(value)!r}")
+
+
+def parcel_cfg(formulae, setup, dt, steps_per_launch=0):
+    """abi.ParcelCfg of a CondensationSetup and a time step"""
+    cfg = abi.ParcelCfg()
+    cfg.dt = float(dt)
+    cfg.g_std = float(getattr(formulae.constants, "g_std", G_STD))
+    cfg.rtol_x, cfg.rtol_thd = float(setup.rtol_x), float(setup.rtol_thd)
+    cfg.dt_min, cfg.dt_max = float(setup.dt_cond_range[0]), float(setup.dt_cond_range[1])
+    cfg.RH_rtol = float(setup.RH_rtol)
+    cfg.adaptive, cfg.fuse = int(bool(setup.adaptive)), int(setup.fuse)
+    cfg.multiplier, cfg.max_iters = int(setup.multiplier), int(setup.max_iters)
+    # dynamics/condensation.py:122-131
+    cfg.n_clamp_lo = int(dt / setup.dt_cond_range[1])
+    cfg.n_clamp_hi = int(dt / setup.dt_cond_range[0]) if setup.dt_cond_range[0] != 0 else 0
+    cfg.steps_per_launch = int(steps_per_launch)
+    return cfg
+
+
+def parcel_call(engine, formulae, cfg, *, n_steps, parcel_start, water_mass, multiplicity,
+                dry_volume, kappa, f_org, critical_volume, state, w_mid, profile=None,
+                descriptor=None, general=False):
+    """one `sdm_parcel_run` call with raw engine arrays: `state` / `profile` are dicts of engine
+    arrays by the member names of sdm_parcel_state / sdm_parcel_profile (`profile` may be None or
+    lack members), `w_mid` an engine array of n_steps x n_parcel.  PySDM's default formulae go to
+    the default kernel unless `general` (the two must agree bit for bit)"""
+    if descriptor is None:
+        descriptor = check_formulae(formulae)
+    n_parcel = engine.size(parcel_start) - 1
+    if engine.size(w_mid) != n_steps * n_parcel:
+        raise ValueError("parcel: w_mid must hold n_steps x n_parcel values")
+    c_state = abi.ParcelState()
+    for name in abi.PARCEL_STATE_FIELDS:
+        if engine.size(state[name]) != n_parcel:
+            raise ValueError(f"parcel: state[{name!r}] must hold n_parcel values")
+        setattr(c_state, name, _address(state[name], INT if name in _INT_FIELDS else FLOAT))
+    c_profile = None
+    if profile is not None:
+        c_profile = abi.ParcelProfile()
+        for name in abi.PARCEL_PROFILE_FIELDS:
+            array = profile.get(name)
+            if array is not None and engine.size(array) != n_steps * n_parcel:
+                raise ValueError(f"parcel: profile[{name!r}] must hold n_steps x n_parcel values")
+            setattr(c_profile, name,
+                    _address(array, INT if name.startswith("n_") else FLOAT))
+    consts = [float(getattr(formulae.constants, name)) for name in CONSTANT_NAMES]
+    engine.call_parcel(
+        "sdm_parcel_run", cfg, int(n_steps), int(n_parcel), int(engine.size(water_mass)),
+        parcel_start, water_mass, multiplicity, dry_volume, kappa, f_org, critical_volume,
+        c_state, w_mid, c_profile, consts,
+        None if is_default(descriptor) and not general else descriptor)
+
+
+class ParcelRunner:  # pylint: disable=too-many-instance-attributes
+    """an ensemble of adiabatic parcels; see the module's docstring.
+
+    `counts[c]` rows of the per-droplet arrays (`multiplicity`, `water_mass`, `dry_volume`,
+    `kappa`, `f_org`), in order, belong to parcel c.  `T0, p0, qv0, w, mass_of_dry_air, z0` are
+    scalars or arrays of n_parcel; `w` may be a callable of time, or a list of n_parcel numbers
+    and callables.  `steps_per_launch` (fused route): 0 for the library's default."""
+
+    def __init__(self, engine, formulae, setup, *, dt, T0, p0, qv0, w, mass_of_dry_air, z0=0,
+                 counts, multiplicity, water_mass, dry_volume, kappa, f_org=None, route="fused",
+                 steps_per_launch=0, general=False):
+        if route not in ROUTES:
+            raise ValueError(f"route must be one of {ROUTES}, not {route!r}")
+        check_hydrostatics(formulae)
+        self.engine, self.formulae, self.setup = engine, formulae, setup
+        self.descriptor = check_formulae(formulae)
+        self.ventilated = _option_name(formulae.ventilation) != "Neglect"
+        if route == "fused":
+            if engine.parcel_library is None:
+                raise NotImplementedError(
+                    f"engine `{engine.name}` has no parcel library: route='fused' is not "
+                    "available on it (route='stages' is)")
+            if self.ventilated:
+                raise NotImplementedError(
+                    "ventilation other than Neglect needs a fall velocity per droplet per step: "
+                    "it stays on route='stages'")
+        elif self.ventilated:
+            raise NotImplementedError(
+                "the parcel's stage route with ventilation needs a terminal velocity law: use "
+                "CondensationRunner with a Population")
+        if setup.dt_cond_range[0] == 0:
+            raise NotImplementedError("dt_cond_range[0] == 0")
+        self.route, self.general = route, bool(general)
+        self.dt = float(dt)
+        self.cfg = parcel_cfg(formulae, setup, self.dt, steps_per_launch)
+        counts = np.asarray(counts, dtype=np.int64).reshape(-1)
+        if counts.size == 0 or (counts <= 0).any():
+            raise ValueError("every parcel needs at least one super-droplet")
+        self.n_parcel = n_parcel = int(counts.size)
+        self.parcel_start_host = np.concatenate(([0], np.cumsum(counts))).astype(np.int64)
+        self.n_sd = n_sd = int(self.parcel_start_host[-1])
+        const = formulae.constants
+
+        def per_parcel(value, name):
+            out = np.broadcast_to(np.asarray(value, dtype=float), (n_parcel,)).copy()
+            if not np.isfinite(out).all():
+                raise ValueError(f"{name} must be finite")
+            return out
+
+        def column(value, name, dtype):
+            out = np.ascontiguousarray(value, dtype=dtype).reshape(-1)
+            if out.size != n_sd:
+                raise ValueError(f"{name} must hold sum(counts) = {n_sd} values")
+            return engine.upload(out)
+
+        self.w = self._updrafts(w)
+        T0, p0, qv0 = per_parcel(T0, "T0"), per_parcel(p0, "p0"), per_parcel(qv0, "qv0")
+        # Parcel.register, parcel.py:51-71 (trivia.p_d, rhod_of_pd_T, th_std)
+        pd0 = p0 * (1 - 1 / (1 + const.eps / qv0))
+        rhod0 = pd0 / const.Rd / T0
+        thd0 = T0 * np.power(const.p1000 / pd0, const.Rd_over_c_pd)
+        up = engine.upload
+        self.state = {
+            "z": up(per_parcel(z0, "z0")), "rhod": up(rhod0), "thd": up(thd0), "qv": up(qv0),
+            "T": engine.empty(n_parcel, FLOAT), "p": engine.empty(n_parcel, FLOAT),
+            "RH": engine.empty(n_parcel, FLOAT), "qv_prev": up(qv0.copy()),
+            "mass_of_dry_air": up(per_parcel(mass_of_dry_air, "mass_of_dry_air")),
+            "n_substeps": engine.full(n_parcel, INT, -1 if setup.adaptive else setup.substeps),
+            "n_activating": engine.full(n_parcel, INT, -1),
+            "n_deactivating": engine.full(n_parcel, INT, -1),
+            "n_ripening": engine.full(n_parcel, INT, -1),
+            "RH_max": engine.full(n_parcel, FLOAT, np.nan),
+            "steps_done": engine.zeros(n_parcel, INT),
+            "failed_step": engine.full(n_parcel, INT, -1),
+        }
+        temperature_pressure_rh_call(engine, formulae, self.state["rhod"], self.state["thd"],
+                                     self.state["qv"], self.state["T"], self.state["p"],
+                                     self.state["RH"], n_parcel)
+        self.parcel_start = up(self.parcel_start_host)
+        self.multiplicity = column(multiplicity, "multiplicity", np.int64)
+        self.water_mass = column(water_mass, "water_mass", float)
+        self.dry_volume = column(dry_volume, "dry_volume", float)
+        self.kappa = column(np.broadcast_to(np.asarray(kappa, dtype=float), (n_sd,)), "kappa",
+                            float)
+        self.f_org = column(np.zeros(n_sd) if f_org is None else f_org, "f_org", float)
+        self.critical_volume = engine.full(n_sd, FLOAT, np.nan)
+        self.n_steps = 0  # time steps asked for so far: the clock of w(t)
+        self.last_profile = None
+        self._reported = set()
+
+    # ---- construction from a spectrum ---------------------------------------------------------
+    @classmethod
+    def from_spectrum(cls, engine, formulae, setup, *, dt, T0, p0, qv0, w, mass_of_dry_air,
+                      spectrum, kappa, n_sd, n_parcel=1, z0=0, f_org=None,
+                      sampling="constant_multiplicity", **kwargs):
+        """`n_parcel` parcels of `n_sd` super-droplets each, sampled from the dry-radius `spectrum`
+        (per kg of dry air) and brought to Koehler equilibrium with each parcel's initial air by
+        `initialisation.wet_aerosol`; multiplicity = discretise(n_per_kg * mass_of_dry_air), what
+        `Parcel.init_attributes` callers pass as n_in_dv"""
+        from . import initialisation  # pylint: disable=import-outside-toplevel
+        from .condensation import AmbientColumns  # pylint: disable=import-outside-toplevel
+
+        const = formulae.constants
+        broadcast = lambda v: np.broadcast_to(np.asarray(v, dtype=float), (n_parcel,))  # noqa: E731
+        T0b, p0b, qv0b, mass = broadcast(T0), broadcast(p0), broadcast(qv0), broadcast(
+            mass_of_dry_air)
+        pd0 = p0b * (1 - 1 / (1 + const.eps / qv0b))
+        ambient = AmbientColumns(engine, formulae, rhod=pd0 / const.Rd / T0b,
+                                 thd=T0b * np.power(const.p1000 / pd0, const.Rd_over_c_pd),
+                                 qv=qv0b)
+        cells = np.repeat(np.arange(n_parcel, dtype=np.int64), n_sd)
+        sampler = initialisation.SAMPLERS[sampling] if isinstance(sampling, str) else sampling
+
+        def tiled(spec, _):  # every parcel gets the same n_sd bins of the spectrum
+            r_dry, n_per_kg = sampler(spec, n_sd)
+            return np.tile(r_dry, n_parcel), np.tile(n_per_kg, n_parcel)
+
+        forg = None if f_org is None else np.broadcast_to(np.asarray(f_org, dtype=float),
+                                                          (n_parcel * n_sd,)).copy()
+        drops = initialisation.wet_aerosol(engine, formulae, ambient, spectrum=spectrum,
+                                           kappa=kappa, n_sd=n_parcel * n_sd, cell_id=cells,
+                                           f_org=forg, sampling=tiled)
+        multiplicity = initialisation.discretise_multiplicities(drops["n_per_kg"] * mass[cells])
+        return cls(engine, formulae, setup, dt=dt, T0=T0, p0=p0, qv0=qv0, w=w,
+                   mass_of_dry_air=mass_of_dry_air, z0=z0, counts=np.full(n_parcel, n_sd),
+                   multiplicity=multiplicity, water_mass=drops["water_mass"],
+                   dry_volume=drops["dry_volume"], kappa=drops["kappa"], f_org=forg, **kwargs)
+
+    # ---- updrafts -------------------------------------------------------------------------------
+    def _updrafts(self, w):
+        if callable(w):
+            return [w] * self.n_parcel
+        if isinstance(w, (list, tuple)) and any(callable(item) for item in w):
+            if len(w) != self.n_parcel:
+                raise ValueError("w must hold one entry per parcel")
+            return [item if callable(item) else (lambda _, value=float(item): value)
+                    for item in w]
+        values = np.broadcast_to(np.asarray(w, dtype=float), (self.n_parcel,))
+        return [(lambda _, value=float(value): value) for value in values]
+
+    def w_mid(self, n_steps):
+        """w((k + 1/2) dt) of the next `n_steps` steps (parcel.py:109), n_steps x n_parcel"""
+        out = np.empty((n_steps, self.n_parcel))
+        for k in range(n_steps):
+            t = (self.n_steps + k + 1 / 2) * self.dt
+            for c, w in enumerate(self.w):
+                out[k, c] = w(t)
+        if not np.isfinite(out).all() or (out == 0).any():
+            raise ValueError("parcel: the updraft must be finite and non-zero at every step's "
+                             "mid-point (the step divides by it)")
+        return out
+
+    # ---- running ----------------------------------------------------------------------------------
+    def run(self, n_steps, profile=True):
+        """`n_steps` further time steps of every parcel that has not failed; returns the profile
+        (host arrays of n_steps x n_parcel by the names of sdm_parcel_profile; entries of steps a
+        failed parcel did not carry out are NaN / -1) or None.  Raises
+        RuntimeError("Condensation failed", parcel, step) after the call for the first parcel whose
+        solver failed in it: the other parcels' state stays valid (and the profile is kept in
+        `last_profile`); a failed parcel is skipped from then on"""
+        n_steps = int(n_steps)
+        if n_steps < 0:
+            raise ValueError("n_steps must not be negative")
+        eng, n_parcel = self.engine, self.n_parcel
+        record = None
+        if n_steps > 0:
+            w_mid = self.w_mid(n_steps)
+            if profile:
+                record = {name: eng.full(n_steps * n_parcel, INT, -1) if name.startswith("n_")
+                          else eng.full(n_steps * n_parcel, FLOAT, np.nan)
+                          for name in abi.PARCEL_PROFILE_FIELDS}
+            if self.route == "fused":
+                parcel_call(eng, self.formulae, self.cfg, n_steps=n_steps,
+                            parcel_start=self.parcel_start, water_mass=self.water_mass,
+                            multiplicity=self.multiplicity, dry_volume=self.dry_volume,
+                            kappa=self.kappa, f_org=self.f_org,
+                            critical_volume=self.critical_volume, state=self.state,
+                            w_mid=eng.upload(w_mid.reshape(-1)), profile=record,
+                            descriptor=self.descriptor, general=self.general)
+            else:
+                self._run_stages(w_mid, record)
+            self.n_steps += n_steps
+        out = None
+        if record is not None:
+            out = {name: eng.download(array).reshape(n_steps, n_parcel)
+                   for name, array in record.items()}
+        self.last_profile = out
+        failed = eng.download(self.state["failed_step"])
+        for parcel in np.flatnonzero(failed >= 0):
+            if int(parcel) not in self._reported:
+                self._reported.update(int(p) for p in np.flatnonzero(failed >= 0))
+                raise RuntimeError("Condensation failed", int(parcel), int(failed[parcel]))
+        return out
+
+    def _latent_heat(self, T, scratch):
+        """formulae.latent_heat_vapourisation.lv(T) in the library's arithmetic: Kirchhoff and
+        Constant are plain doubles; Lowe2019's power goes through `sdm_elementwise_f64` (the
+        library's pow, which the kernels evaluate), one element"""
+        const = self.formulae.constants
+        choice = self.descriptor.option[_LV]
+        if choice == 1:
+            return const.l_tri
+        if choice == 2:
+            eng = self.engine
+            eng.fill(scratch, const.T_tri / T)
+            eng.call("sdm_elementwise_f64", 4, scratch, scratch, None,
+                     float(const.l_l19_a + const.l_l19_b * T), 1)
+            return const.l_tri * float(eng.download(scratch)[0])
+        return const.l_tri + (const.c_pv - const.c_pw) * (T - const.T_tri)
+
+    def _run_stages(self, w_mid, record):  # pylint: disable=too-many-locals,too-many-statements
+        """the time step of include/sdm_parcel.h with the stage symbols, parcel after parcel"""
+        eng, const, cfg, setup = self.engine, self.formulae.constants, self.cfg, self.setup
+        host = {name: eng.download(array) for name, array in self.state.items()}
+        rows = {name: (eng.download(array) if array is not None else None)
+                for name, array in (record or {}).items()}
+        one = {name: eng.empty(1, FLOAT) for name in
+               ("rhod", "thd", "qv", "prhod", "pthd", "pqv", "T", "p", "RH", "RH_max", "lv")}
+        counters = {name: eng.empty(1, INT) for name in
+                    ("n_substeps", "n_activating", "n_deactivating", "n_ripening")}
+        success = eng.zeros(1, np.uint8)
+        zero = eng.zeros(1, INT)
+        most = int(np.diff(self.parcel_start_host).max())
+        v_wet, backup = eng.empty(most, FLOAT), eng.empty(most, FLOAT)
+        cell = eng.zeros(most, INT)
+        identity = eng.upload(np.arange(most, dtype=np.int64))
+        dt_range = (setup.dt_cond_range[0], min(setup.dt_cond_range[1], self.dt))
+        n_parcel = self.n_parcel
+        for c in range(n_parcel):
+            if host["failed_step"][c] >= 0:
+                continue
+            r0, r1 = (int(v) for v in self.parcel_start_host[c:c + 2])
+            n = r1 - r0
+            cell_start = eng.upload(np.array([0, n], dtype=np.int64))
+            mass = self.water_mass[r0:r1]
+            for k in range(w_mid.shape[0]):
+                T, p = float(host["T"][c]), float(host["p"][c])
+                rhod, thd, qv = (float(host[v][c]) for v in ("rhod", "thd", "qv"))
+                w, dt = float(w_mid[k, c]), self.dt
+                delta = float(host["qv_prev"][c]) - qv
+                qv_mid = qv - delta / 2
+                lv = self._latent_heat(T, one["lv"])
+                Rq = const.Rv / (1 / qv_mid + 1) + const.Rd / (1 + qv_mid)
+                cp = const.c_pv / (1 / qv_mid + 1) + const.c_pd / (1 + qv_mid)
+                rho = p / Rq / T
+                dql_dz = delta / w / dt
+                drho_dz = (cfg.g_std / T * rho * (Rq / cp - 1)
+                           - p * lv / cp / (T * T) * dql_dz) / Rq
+                z = float(host["z"][c]) + dt * w
+                prhod = rhod + dt * (w * drho_dz)
+                dv = float(host["mass_of_dry_air"][c]) / ((prhod + rhod) / 2)
+                for name, value in (("rhod", rhod), ("thd", thd), ("qv", qv), ("prhod", prhod),
+                                    ("pthd", thd), ("pqv", qv), ("T", T)):
+                    eng.fill(one[name], value)
+                eng.fill(counters["n_substeps"], int(host["n_substeps"][c]))
+                eng.call("sdm_volume_of_water_mass", v_wet[:n], mass, n, float(const.rho_w))
+                eng.assign(backup[:n], mass)
+                critical_volume_call(eng, self.formulae, self.critical_volume[r0:r1],
+                                     self.kappa[r0:r1], self.f_org[r0:r1],
+                                     self.dry_volume[r0:r1], v_wet[:n], one["T"], cell[:n], n)
+                condensation_call(
+                    eng, formulae=self.formulae, n_sd=n, n_cell=1, cell_start=cell_start,
+                    water_mass=mass, v_cr=self.critical_volume[r0:r1],
+                    multiplicity=self.multiplicity[r0:r1], vdry=self.dry_volume[r0:r1],
+                    idx=identity[:n], rhod=one["rhod"], thd=one["thd"],
+                    water_vapour_mixing_ratio=one["qv"], dv=dv, prhod=one["prhod"],
+                    pthd=one["pthd"], predicted_water_vapour_mixing_ratio=one["pqv"],
+                    kappa=self.kappa[r0:r1], f_org=self.f_org[r0:r1], rtol_x=setup.rtol_x,
+                    rtol_thd=setup.rtol_thd, timestep=dt, counters=counters, cell_order=zero,
+                    RH_max=one["RH_max"], success=success, reynolds_number=None,
+                    air_density=None, air_dynamic_viscosity=None, dt_range=dt_range,
+                    adaptive=setup.adaptive, fuse=setup.fuse, multiplier=setup.multiplier,
+                    RH_rtol=setup.RH_rtol, max_iters=setup.max_iters, general=self.general,
+                    descriptor=self.descriptor)
+                if not eng.download(success)[0]:
+                    eng.assign(mass, backup[:n])
+                    host["failed_step"][c] = host["steps_done"][c]
+                    break
+                temperature_pressure_rh_call(eng, self.formulae, one["prhod"], one["pthd"],
+                                             one["pqv"], one["T"], one["p"], one["RH"], 1)
+                n_sub = int(eng.download(counters["n_substeps"])[0])
+                if setup.adaptive:  # dynamics/condensation.py:122-131
+                    n_sub = min(max(n_sub, int(cfg.n_clamp_lo)), int(cfg.n_clamp_hi))
+                host["qv_prev"][c] = qv
+                host["z"][c], host["rhod"][c] = z, prhod
+                host["thd"][c] = eng.download(one["pthd"])[0]
+                host["qv"][c] = eng.download(one["pqv"])[0]
+                for name in ("T", "p", "RH", "RH_max"):
+                    host[name][c] = eng.download(one[name])[0]
+                host["n_substeps"][c] = n_sub
+                for name in ("n_activating", "n_deactivating", "n_ripening"):
+                    host[name][c] = eng.download(counters[name])[0]
+                host["steps_done"][c] += 1
+                for name, row in rows.items():
+                    if row is not None:
+                        row[k * n_parcel + c] = host[name][c]
+        for name, array in self.state.items():
+            eng.assign(array, eng.upload(host[name]))
+        for name, row in rows.items():
+            if row is not None:
+                eng.assign(record[name], eng.upload(row))
+
+    # ---- state --------------------------------------------------------------------------------------
+    def snapshot(self):
+        """host copies of everything a later `restore` needs: the parcels' state arrays, the
+        per-droplet water masses and critical volumes, and the clock of w(t)"""
+        down = self.engine.download
+        out = {name: down(array) for name, array in self.state.items()}
+        out["water_mass"] = down(self.water_mass)
+        out["critical_volume"] = down(self.critical_volume)
+        out["n_steps"] = self.n_steps
+        return out
+
+    def restore(self, state):
+        """sets the state to a given one (a `snapshot`, or any dict with some of its entries):
+        qv_prev, the counters, steps_done and failed_step included.  Where rhod, thd or qv are given
+        without T, p and RH, these are recomputed from them (`sdm_temperature_pressure_rh`)"""
+        eng = self.engine
+        for name, value in state.items():
+            if name == "n_steps":
+                self.n_steps = int(value)
+                continue
+            target = {"water_mass": self.water_mass,
+                      "critical_volume": self.critical_volume}.get(name, self.state.get(name))
+            if target is None:
+                raise KeyError(name)
+            dtype = INT if name in _INT_FIELDS else FLOAT
+            value = np.ascontiguousarray(np.broadcast_to(
+                np.asarray(value, dtype=dtype), (eng.size(target),)))
+            eng.assign(target, eng.upload(value))
+        if {"rhod", "thd", "qv"} & set(state) and not {"T", "p", "RH"} & set(state):
+            temperature_pressure_rh_call(eng, self.formulae, self.state["rhod"],
+                                         self.state["thd"], self.state["qv"], self.state["T"],
+                                         self.state["p"], self.state["RH"], self.n_parcel)
+        failed = eng.download(self.state["failed_step"])
+        self._reported = {int(p) for p in np.flatnonzero(failed >= 0)}

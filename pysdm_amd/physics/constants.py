@@ -70,6 +70,7 @@ l_tri = 2500711.849262262
 T_tri = 273.16
 T0 = 273.15
 p1000 = 100000.0
+g_std = 9.80665
 eps = 0.6219453958862249
 D0 = 2.26e-05
 K0 = 0.024

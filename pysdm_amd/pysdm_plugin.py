@@ -499,3 +499,108 @@ def fuse(dynamic):
     if type(dynamic).__name__ == "RelaxedVelocity":
         return FusedRelaxedVelocity(dynamic)
     return FusedCollision(dynamic)
+
+
+# ---- the adiabatic parcel: whole ascents in one call -------------------------------------------------
+_PARCEL_VARS = {"z": "z", "rhod": "rhod", "thd": "thd", "qv": "water_vapour_mixing_ratio",
+                "T": "T", "p": "p", "RH": "RH"}
+
+
+def run_parcel(particulator, steps):
+    """`steps` time steps of a built `Particulator` whose environment is a `Parcel` and whose
+    dynamics are exactly `AmbientThermodynamics` and `Condensation`, in ONE `sdm_parcel_run` on the
+    particulator's own arrays (include/sdm_parcel.h; anything else: ValueError).  It leaves the
+    particulator as `particulator.run(steps)` would: the water masses (marked updated), the
+    environment's current values and the previous ones that `sync_parcel_vars` reads next, the
+    dynamic's counters, `rh_max` and `success`, and `n_steps`.
+
+    Observers and products are NOT notified per step: there is no per-step hook inside the kernel.
+    Read products before and after, or keep `particulator.run` where every step must be seen.
+    Returns the profile (host arrays of `steps` values by the names of sdm_parcel_profile)"""
+    from . import parcel as _parcel  # pylint: disable=import-outside-toplevel
+    from .condensation import CondensationSetup, check_formulae  # pylint: disable=import-outside-toplevel
+    from .engine import FLOAT, INT  # pylint: disable=import-outside-toplevel
+
+    env = particulator.environment
+    if type(env).__name__ != "Parcel":
+        raise ValueError(f"run_parcel needs a Parcel environment, not {type(env).__name__}")
+    if sorted(particulator.dynamics) != ["AmbientThermodynamics", "Condensation"]:
+        raise ValueError("run_parcel needs exactly the dynamics AmbientThermodynamics and "
+                         f"Condensation, not {sorted(particulator.dynamics)}")
+    if "a_w_ice" in env.variables:
+        raise ValueError("run_parcel: mixed_phase=True is not served")
+    dynamic = particulator.dynamics["Condensation"]
+    if not dynamic.enable or not dynamic.update_thd:
+        raise ValueError("run_parcel needs Condensation(enable=True, update_thd=True)")
+    steps = int(steps)
+    if steps <= 0:
+        return None
+    formulae, eng = particulator.formulae, particulator.backend.engine
+    _parcel.check_hydrostatics(formulae)
+    if _parcel._option_name(formulae.ventilation) != "Neglect":  # pylint: disable=protected-access
+        raise ValueError("run_parcel: ventilation other than Neglect stays on particulator.run")
+    descriptor = check_formulae(formulae)
+    setup = CondensationSetup(
+        rtol_x=dynamic.rtol_x, rtol_thd=dynamic.rtol_thd,
+        dt_cond_range=tuple(dynamic.dt_cond_range), adaptive=bool(dynamic.adaptive),
+        substeps=1, max_iters=int(dynamic.max_iters)) if dynamic.adaptive else CondensationSetup(
+            rtol_x=dynamic.rtol_x, rtol_thd=dynamic.rtol_thd,
+            dt_cond_range=tuple(dynamic.dt_cond_range), adaptive=False,
+            substeps=int(getattr(dynamic, "_Condensation__substeps", 1)),
+            max_iters=int(dynamic.max_iters))
+    dt = float(particulator.dt)
+    cfg = _parcel.parcel_cfg(formulae, setup, dt)
+
+    attrs = particulator.attributes
+    idx = getattr(attrs, _PRIVATE + "idx")
+    n_sd = int(len(idx))
+    if n_sd != int(particulator.n_sd) or not np.array_equal(
+            eng.download(idx.data)[:n_sd], np.arange(n_sd)):
+        raise ValueError("run_parcel needs every super-droplet valid and in row order")
+    current, tmp = env._values["current"], env._tmp  # pylint: disable=protected-access
+    before = {name: float(eng.download(current[var].data)[0])
+              for name, var in _PARCEL_VARS.items()}
+    qv_prev_before = float(eng.download(tmp["water_vapour_mixing_ratio"].data)[0])
+    state = {name: current[var].data for name, var in _PARCEL_VARS.items()}
+    state["qv_prev"] = tmp["water_vapour_mixing_ratio"].data
+    state["mass_of_dry_air"] = eng.upload(np.array([env.mass_of_dry_air], dtype=float))
+    for name in ("n_substeps", "n_activating", "n_deactivating", "n_ripening"):
+        state[name] = dynamic.counters[name].data
+    state["RH_max"] = dynamic.rh_max.data
+    state["steps_done"] = eng.zeros(1, INT)
+    state["failed_step"] = eng.full(1, INT, -1)
+    w_mid = np.array([float(env.w((particulator.n_steps + k + 1 / 2) * dt))
+                      for k in range(steps)])
+    if not np.isfinite(w_mid).all() or (w_mid == 0).any():
+        raise ValueError("run_parcel: the updraft must be finite and non-zero at every step's "
+                         "mid-point")
+    record = {name: eng.full(steps, FLOAT, np.nan) for name in _PARCEL_VARS}
+    _parcel.parcel_call(
+        eng, formulae, cfg, n_steps=steps,
+        parcel_start=eng.upload(np.array([0, n_sd], dtype=np.int64)),
+        water_mass=attrs["signed water mass"].data, multiplicity=attrs["multiplicity"].data,
+        dry_volume=attrs["dry volume"].data, kappa=attrs["kappa"].data,
+        f_org=attrs["dry volume organic fraction"].data,
+        critical_volume=eng.empty(n_sd, FLOAT), state=state, w_mid=eng.upload(w_mid),
+        profile=record, descriptor=descriptor)
+    attrs.mark_updated("signed water mass")
+    done = int(eng.download(state["steps_done"])[0])
+    rows = {name: eng.download(array) for name, array in record.items()}
+    # what notify() leaves behind: _tmp holds the values before the last step carried out
+    if done > 0:
+        previous = {name: (rows[name][done - 2] if done >= 2 else before[name])
+                    for name in _PARCEL_VARS}
+        for name, var in _PARCEL_VARS.items():
+            eng.fill(tmp[var].data, float(previous[name]))
+        before_previous = (rows["qv"][done - 3] if done >= 3
+                           else before["qv"] if done == 2 else qv_prev_before)
+        env.delta_liquid_water_mixing_ratio = before_previous - previous["qv"]
+        env.mesh.dv = formulae.trivia.volume_of_density_mass(
+            (rows["rhod"][done - 1] + previous["rhod"]) / 2, env.mass_of_dry_air)
+        env._values["predicted"] = None  # pylint: disable=protected-access
+        eng.fill(dynamic.success.data, True)
+        particulator.n_steps += done
+    if done < steps:
+        eng.fill(dynamic.success.data, False)
+        raise RuntimeError("Condensation failed")
+    return rows

@@ -1,0 +1,119 @@
+#!/usr/bin/env python3
+"""Times the adiabatic parcel on the GPU (pysdm_amd.parcel.ParcelRunner): ensembles of 1, 16, 256
+and 1024 parcels of 256 super-droplets, 100 steps of 1 s, updrafts spread over 0.2 .. 5 m/s, with
+PySDM's default formulae and with the Lowe-2019 set (tests/condensation_formulae_cases.py).
+
+The fused route (`sdm_parcel_run`: one call, the steps inside the kernel) at every size; the stage
+route (the same step written with the symbols of include/sdm_condensation.h, a Python loop over
+parcels and steps with its read-backs) at 1 and 16 parcels only - it is a loop over parcels, so
+its larger sizes would say nothing new, and nothing here extrapolates it.  The stage route is the
+yardstick: it uses only symbols that existed before the fused route.
+
+Timed with HIP events on the stream around `run(steps, profile=False)`, every repetition from the
+same restored state, a warm-up call first; the figure is the median of --reps calls.  The longest
+single launch is measured separately: the same ascent as calls of `steps_per_launch` steps, each
+one launch, the slowest of them reported.  Writes profiles/parcel_timing.json and prints it; a
+measurement, not a test: no threshold, no ratio fixed in advance.
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+SIZES = (1, 16, 256, 1024)
+STAGE_SIZES = (1, 16)
+N_SD, STEPS, DT = 256, 100, 1.0
+
+
+def make_runner(kind, n_parcel, route, steps_per_launch, engine=None):
+    from pysdm_amd import spectra  # pylint: disable=import-outside-toplevel
+    from pysdm_amd.condensation import CondensationSetup  # pylint: disable=import-outside-toplevel
+    from pysdm_amd.engine import HipEngine  # pylint: disable=import-outside-toplevel
+    from pysdm_amd.parcel import ParcelRunner  # pylint: disable=import-outside-toplevel
+    from tests.parcel_cases import formulae_of  # pylint: disable=import-outside-toplevel
+
+    updrafts = np.linspace(0.2, 5.0, n_parcel) if n_parcel > 1 else np.array([2.0])
+    return ParcelRunner.from_spectrum(
+        engine or HipEngine.get(), formulae_of(kind), CondensationSetup(), dt=DT, T0=290.0,
+        p0=100000.0, qv0=0.012, w=updrafts, mass_of_dry_air=1.0,
+        spectrum=spectra.Lognormal(norm_factor=60e6 / 1.18, m_mode=0.04e-6, s_geom=1.4),
+        kappa=1.28, f_org=None if kind == "default" else 0.3, n_sd=N_SD, n_parcel=n_parcel,
+        route=route, steps_per_launch=steps_per_launch)
+
+
+def timed(runner, start, steps, reps, warmup):
+    import torch  # pylint: disable=import-outside-toplevel
+
+    samples = []
+    for rep in range(warmup + reps):
+        runner.restore(start)
+        begin, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        begin.record()
+        runner.run(steps, profile=False)
+        end.record()
+        end.synchronize()
+        if rep >= warmup:
+            samples.append(begin.elapsed_time(end))
+    return samples
+
+
+def measure(kind, n_parcel, route, reps, warmup, steps_per_launch):
+    runner = make_runner(kind, n_parcel, route, steps_per_launch)
+    start = runner.snapshot()
+    samples = timed(runner, start, STEPS, reps, warmup)
+    final = runner.snapshot()
+    assert (final["failed_step"] == -1).all() and (final["steps_done"] == STEPS).all()
+    ms = float(np.median(samples))
+    out = {"formulae": kind, "route": route, "n_parcel": n_parcel, "n_sd_per_parcel": N_SD,
+           "steps": STEPS, "reps": reps, "ms_median": round(ms, 3),
+           "ms_min": round(float(np.min(samples)), 3), "ms_max": round(float(np.max(samples)), 3),
+           "ms_per_parcel_step": round(ms / (n_parcel * STEPS), 5),
+           "n_substeps_last": [int(final["n_substeps"].min()), int(final["n_substeps"].max())],
+           "RH_max_last": round(float(final["RH_max"].max()), 5)}
+    if route == "fused":
+        per_launch = steps_per_launch or SPL_DEFAULT
+        out["steps_per_launch"] = per_launch
+        runner.restore(start)
+        launches = []
+        for _ in range(0, STEPS, per_launch):  # one launch per call
+            state = runner.snapshot()
+            launches.append(float(np.median(timed(runner, state, per_launch, 1, 0))))
+        out["longest_launch_ms"] = round(max(launches), 3)
+        out["launches"] = len(launches)
+    return out
+
+
+SPL_DEFAULT = 16  # SDM_PARCEL_STEPS_PER_LAUNCH of include/sdm_parcel.h
+
+
+def main():
+    parser = argparse.ArgumentParser()
+    parser.add_argument("--reps", type=int, default=5)
+    parser.add_argument("--warmup", type=int, default=1)
+    parser.add_argument("--steps-per-launch", type=int, default=0, help="0: the library's default")
+    parser.add_argument("--out", default=os.path.join(ROOT, "profiles", "parcel_timing.json"))
+    args = parser.parse_args()
+    results = []
+    for kind in ("default", "lowe2019"):
+        for n_parcel in SIZES:
+            results.append(measure(kind, n_parcel, "fused", args.reps, args.warmup,
+                                   args.steps_per_launch))
+            print(json.dumps(results[-1]), flush=True)
+        for n_parcel in STAGE_SIZES:
+            results.append(measure(kind, n_parcel, "stages", args.reps, args.warmup, 0))
+            print(json.dumps(results[-1]), flush=True)
+    text = json.dumps({"workload": f"{N_SD} super-droplets per parcel, {STEPS} steps of {DT} s, "
+                                   "updrafts 0.2 .. 5 m/s (2 m/s for one parcel)",
+                       "results": results}, indent=1)
+    with open(args.out, "w", encoding="utf-8") as out:
+        out.write(text + "\n")
+    print("wrote", args.out)
+
+
+if __name__ == "__main__":
+    main()
