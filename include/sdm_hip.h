@@ -87,10 +87,10 @@ const char *sdm_phase_name(int phase);
                                  384-position one would be taken */
 #define SDM_CELL_SHAPE_1024 2 /* one workgroup of 1024 per CU, cells <= 6144: fewer cells than CUs */
 #define SDM_CELL_SHAPE_256 3  /* four workgroups of 256 per CU, cells <= 2816 */
-/* Four A/B switches (measurements, and tests that want both implementations in one process).
+/* Five A/B switches (measurements, and tests that want both implementations in one process).
  * Results are identical either way.  The defaults can also be set for a whole process through
  * the environment, read when a context is created: SDM_REC_FORMAT=records, SDM_NO_PRESORT=1,
- * SDM_CELL_COPY=0, SDM_WALK_LOCAL=0.
+ * SDM_CELL_COPY=0, SDM_WALK_LOCAL=0, SDM_NARROW_STEP=0.
  * SDM_OPT_REC_FORMAT: SDM_REC_FORMAT_AUTO (default) = successor words where they apply (one cell,
  *   the shuffle left to the pair kernels, up to 2^22 positions); SDM_REC_FORMAT_RECORDS = the
  *   packed 16-byte records of rounds 1-3 everywhere.
@@ -103,13 +103,17 @@ const char *sdm_phase_name(int phase);
  *   take their workgroups in grid order and every hop of a walk from global memory; 0 (default) =
  *   the workgroups of one event tile get block numbers 8 apart (one XCD's L2 holds the tile's
  *   successor words), and k_pair_all_sort resolves a walk's first hop from the tile's segment in
- *   LDS.                                                                                        */
+ *   LDS.
+ * SDM_OPT_NARROW_STEP: 1 = inside a call of several steps (one cell, non-adaptive) the permutation
+ *   goes from a step's pair kernel to the next step's shuffle build as int64_t; 0 (default) = as
+ *   32-bit ids.  Nothing narrow is left in the state when a call returns.                        */
 #define SDM_OPT_REC_FORMAT 3
 #define SDM_REC_FORMAT_AUTO 0
 #define SDM_REC_FORMAT_RECORDS 1
 #define SDM_OPT_NO_PRESORT 4
 #define SDM_OPT_NO_CELL_COPY 5
 #define SDM_OPT_WALK_LOCAL 6
+#define SDM_OPT_NARROW_STEP 7
 int sdm_ctx_set_option(sdm_ctx *ctx, int option, int64_t value);
 /* counters since the context was created / last cleared (host-side bookkeeping of the library):
  * re-sorts after a compaction done by the closed form; asked for and refused by the device; not

@@ -117,6 +117,10 @@ struct FusedArgs {
   // positions per thread) and write the permuted, pair-sorted idx once; NULL otherwise
   const void *rec;  // records of layout rec_fmt (shuffle_device.h: SDM_REC_*)
   int rec_fmt;
+  // inside a call (one cell, non-adaptive, the next step's tile sort riding along): bit 0 = `idx`
+  // points to int32_t ids - the next build reads them so - bit 1 = `idx_prev` does.  (In what was
+  // padding: every other member lies where it lay)
+  int narrow;
   const int32_t *ovf_head, *ovf_next;
   // successor words: events per tile of the build (shuffle_build.h) when the pair kernels take
   // their workgroups tile by tile (pair_block), 0 = in grid order; tiles the tables are padded to
@@ -529,6 +533,12 @@ __device__ __forceinline__ double pair_prob_value(const sdm_step_cfg &cfg, const
   return prob;
 }
 
+// the permutation's word at position p: int64_t, or int32_t inside a call (FusedArgs::narrow)
+__device__ __forceinline__ int64_t idx_load(const int64_t *idx, int narrow, int64_t p) {
+  if (NARROW_IDX && narrow) return ((const int32_t *)idx)[p];
+  return idx[p];
+}
+
 // k_pair_all_sort: the words first[2d], first[2d + 1] of the slot, loaded ahead, and the segment of
 // ssucc in LDS that the walk's first look-up may be taken from (seg == NULL: none)
 struct WalkSeg {
@@ -560,8 +570,12 @@ __device__ __forceinline__ PairInfo pair_prob_body(const sdm_step_cfg &cfg, cons
       } else {
         for (int o = 0; o < 2; ++o) {  // unpaired last position / dead tail
           const int64_t p = 2 * d + o;
-          if (p < W) A.idx[p] = walk_id(A.rec, A.rec_fmt, A.ovf_head, A.ovf_next, (int32_t)p, 0);
-          else if (p < cfg.n_sd) A.idx[p] = A.idx_prev[p];
+          int64_t id;
+          if (p < W) id = walk_id(A.rec, A.rec_fmt, A.ovf_head, A.ovf_next, (int32_t)p, 0);
+          else if (p < cfg.n_sd) id = idx_load(A.idx_prev, A.narrow & 2, p);
+          else continue;
+          if (NARROW_IDX && (A.narrow & 1)) ((int32_t *)A.idx)[p] = (int32_t)id;
+          else A.idx[p] = id;
         }
       }
     }
@@ -596,7 +610,9 @@ __device__ __forceinline__ PairInfo pair_prob_body(const sdm_step_cfg &cfg, cons
     const int64_t tn = nj; nj = nk; nk = tn;
     const SD ts = sj; sj = sk; sk = ts;
   }
-  if (swap || traced) {
+  if (NARROW_IDX && (A.narrow & 1)) {  // (traced, one cell: i = 2d - one 8-byte store per slot)
+    *(int2 *)((int32_t *)A.idx + i) = make_int2((int32_t)j, (int32_t)k);
+  } else if (swap || traced) {
     A.idx[i] = j;
     A.idx[i + 1] = k;
   }
@@ -771,8 +787,13 @@ __device__ __forceinline__ void note_deaths(const FusedArgs &A, int64_t segment,
 // `A` (may be NULL): where a sharded run counts its dead
 __device__ __forceinline__ void flag_dead(const sdm_step_cfg &cfg, int64_t *__restrict__ idx,
                                           int64_t pos, int died, const FusedArgs *A = nullptr) {
-  if (died & 1) idx[pos] = cfg.n_sd;
-  if (died & 2) idx[pos + 1] = cfg.n_sd;
+  if (NARROW_IDX && A && (A->narrow & 1)) {  // (`idx` is A->idx there; the flag fits 32 bits)
+    if (died & 1) ((int32_t *)idx)[pos] = (int32_t)cfg.n_sd;
+    if (died & 2) ((int32_t *)idx)[pos + 1] = (int32_t)cfg.n_sd;
+  } else {
+    if (died & 1) idx[pos] = cfg.n_sd;
+    if (died & 2) idx[pos + 1] = cfg.n_sd;
+  }
   if (A && died && A->dead_count) {
     const int k = (died & 1) + (died >> 1);
     const unsigned long long at = atomicAdd(A->dead_count, (unsigned long long)k);
@@ -3353,6 +3374,9 @@ static int collision_step(sdm_ctx *ctx, const sdm_step_cfg *cfg, sdm_step_state 
       // (k_pair_all_sort): no k_bin_sort, and the compaction it skipped is the build's to do
       SortPrologue prologue;
       const bool presorted = ctx->presorted.active && ctx->presorted.owner == (const void *)st;
+      // ... and left the permutation in `cur` as 32-bit ids: the build, its compaction and the
+      // dead-tail copy of this sub-step's pair kernel read it so
+      const bool narrow_in = presorted && ctx->presorted.narrow;
       ctx->presorted.active = false;
       if (presorted)
         sdm_compact_as_prologue(ctx, S.compact, st->multiplicity, cur, N, N, st->ctl, S.cctl,
@@ -3360,8 +3384,9 @@ static int collision_step(sdm_ctx *ctx, const sdm_step_cfg *cfg, sdm_step_state 
       rc = sdm_shuffle_build_async(ctx, S.shuffle, cur, st->cell_start, C, p_shuffle_len, N,
                                    cfg->rng_state_inc, u01_off, &views, N,
                                    ctx->graph_capture ? ctx->gwords : nullptr,
-                                   presorted ? &prologue : nullptr);
+                                   presorted ? &prologue : nullptr, narrow_in);
       if (rc) return rc;
+      A.narrow = narrow_in ? 2 : 0;
       A.rec = views.rec;
       A.rec_fmt = views.fmt;
       A.ovf_head = views.ovf_head;
@@ -3422,6 +3447,11 @@ static int collision_step(sdm_ctx *ctx, const sdm_step_cfg *cfg, sdm_step_state 
         X.n_tiles = B.n_tiles;
         X.p_length = st->cell_start + C;
         X.s_off = sdm_pcg_advance_host(rng_state, rng_inc, off);  // (off: the next draw's start)
+        // the only reader of what this kernel writes to `cur` is the build it sorts for: 32-bit
+        // ids (below P21_MAX on this route), 4 MB less stored here and loaded there at 2^20
+        // (SDM_OPT_NARROW_STEP = 1: int64_t as at the ends of a call)
+        const bool narrow_out = NARROW_IDX && !ctx->opt_wide_step && !sharded;
+        if (narrow_out) A.narrow |= 1;
         const dim3 grid((unsigned)(B.n_tiles + grid_for((N + 1) / 2, BIN_THREADS)));
 #ifdef PAIR_PROFILE
         pair_prof_launch[0] = grid.x; pair_prof_launch[1] = (long long)B.lds_bytes;
@@ -3443,6 +3473,7 @@ static int collision_step(sdm_ctx *ctx, const sdm_step_cfg *cfg, sdm_step_state 
         }
 #undef PAIR_SORT
         ctx->presorted.active = true;
+        ctx->presorted.narrow = narrow_out;
         ctx->presorted.owner = st;
       } else {
         DISPATCH_PAIR(k_pair_all, dim3(grid_for((N + 1) / 2)));

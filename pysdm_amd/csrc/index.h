@@ -47,6 +47,9 @@ struct BuildPrologue {
   // place of its own event in the sorted array, -1: none (from the tile sort); the S words, by
   // that place
   int32_t *chain_links, *loc;
+  // idx0 and compact.idx point to 32-bit ids (the permutation a pair kernel left for the next
+  // step of the same call, fused.hip)
+  int idx_narrow;
   uint32_t *ssucc;
   uint32_t *events;      // packed (shuffle_build.h: ev_pack)
   int32_t *toff, *jarr;  // (jarr: NULL with SDM_REC_CHAIN - `loc` says it all)
@@ -76,7 +79,9 @@ int sdm_shuffle_build_async(sdm_ctx *ctx, char *scratch, const int64_t *idx0,
                             const uint64_t *dev_off = nullptr,
                             // the tile sort was done ahead (k_pair_all_sort): what the build needs
                             // for the compaction it may have to run first
-                            const SortPrologue *presorted = nullptr);
+                            const SortPrologue *presorted = nullptr,
+                            // idx0 (and presorted->idx) are 32-bit ids, not int64_t
+                            bool idx_narrow = false);
 // What ends an adaptive sub-step of a single cell (collision.py:185-187), done by the compaction
 // kernel's last act instead of a launch of its own: refused-breakup count of the counter slots
 // into fctl[4] (slots may be NULL), working length = dt_left[0] != 0 ? valid length : 0, control

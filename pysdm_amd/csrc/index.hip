@@ -169,7 +169,7 @@ static int shuffle_binned_async(sdm_ctx *ctx, char *scratch, int64_t *out, const
                                 const int64_t *p_length, int64_t length_bound, int64_t n_total,
                                 u128 s_off, u128 inc, ShuffleViews *views, int64_t id_bound = -1,
                                 const uint64_t *dev_off = nullptr,
-                                const SortPrologue *presorted = nullptr);
+                                const SortPrologue *presorted = nullptr, bool idx_narrow = false);
 
 // out-of-place core: out[0:length) = shuffled idx0[0:length), out[length:n_total) = idx0[...].
 // u01 == nullptr: draws generated in the kernel from (rng_state_inc, rng_offset).
@@ -295,7 +295,8 @@ static int shuffle_binned_async(sdm_ctx *ctx, char *scratch, int64_t *out, const
                                 const double *u01, const int64_t *cell_start, int64_t n_cell,
                                 const int64_t *p_length, int64_t length_bound, int64_t n_total,
                                 u128 s_off, u128 inc, ShuffleViews *views, int64_t id_bound,
-                                const uint64_t *dev_off, const SortPrologue *presorted) {
+                                const uint64_t *dev_off, const SortPrologue *presorted,
+                                bool idx_narrow) {
   // id_bound: the ids in idx0 are below it (-1: unknown); decides the record layout
   const int64_t both = id_bound > length_bound ? id_bound : length_bound;
   // SDM_REC_CHAIN where the caller's kernels do the walk (`views`); SDM_REC_FORMAT=records keeps
@@ -342,6 +343,7 @@ static int shuffle_binned_async(sdm_ctx *ctx, char *scratch, int64_t *out, const
     sdm_shuffle_sort_buffers(ctx, scratch, length_bound, &ahead);
     ARG_TRY((ahead.loc != nullptr) == (fmt == SDM_REC_CHAIN) && ahead.loc == loc);
   }
+  ARG_TRY(!idx_narrow || (presorted && NARROW_IDX));  // (only a pair kernel leaves 32-bit ids)
   const dim3 block(BIN_THREADS);
   const size_t lds_sort = bin_sort_lds_bytes(nb, tile);
   // (64 KB with three inline slots - two workgroups per CU - 80 KB with four; the prologue of a
@@ -367,6 +369,7 @@ static int shuffle_binned_async(sdm_ctx *ctx, char *scratch, int64_t *out, const
     PhaseScope ph(ctx, SDM_PHASE_SHUFFLE_BUILD);
     BuildPrologue bp;
     memset(&bp, 0, sizeof(bp));
+    bp.idx_narrow = idx_narrow ? 1 : 0;
     if (presorted) {  // sorted by the previous pair kernel; what the build needs to redo it
       bp.compact = *presorted;
       bp.events = events;
@@ -437,7 +440,8 @@ int sdm_shuffle_build_async(sdm_ctx *ctx, char *scratch, const int64_t *idx0,
                             const int64_t *cell_start, int64_t n_cell, const int64_t *p_length,
                             int64_t length_bound, const uint64_t *rng_state_inc,
                             uint64_t rng_offset, ShuffleViews *views, int64_t id_bound,
-                            const uint64_t *dev_off, const SortPrologue *presorted) {
+                            const uint64_t *dev_off, const SortPrologue *presorted,
+                            bool idx_narrow) {
   int rc = sdm_pcg_prepare(ctx, rng_state_inc);
   if (rc) return rc;
   const u128 st = (((u128)rng_state_inc[0]) << 64) | rng_state_inc[1];
@@ -445,7 +449,8 @@ int sdm_shuffle_build_async(sdm_ctx *ctx, char *scratch, const int64_t *idx0,
   // dev_off: the kernels add the stream position themselves (graph replay)
   const u128 s_off = dev_off ? st : sdm_pcg_advance_host(st, inc, rng_offset);
   return shuffle_binned_async(ctx, scratch, nullptr, idx0, nullptr, cell_start, n_cell, p_length,
-                              length_bound, 0, s_off, inc, views, id_bound, dev_off, presorted);
+                              length_bound, 0, s_off, inc, views, id_bound, dev_off, presorted,
+                              idx_narrow);
 }
 
 void sdm_shuffle_sort_buffers(sdm_ctx *ctx, char *scratch, int64_t length_bound, SortBuffers *out) {
@@ -680,9 +685,11 @@ compact_listed_body(int32_t *p, int64_t *__restrict__ idx, const int64_t *__rest
 #define COMPACT_UNROLL 8
 // "dead" of lane's position in COMPACT_UNROLL consecutive tiles (false beyond tile_end / length);
 // val (optional): the idx values read
-template <bool FLAG_ONLY>
+// IDX: the permutation's word, int64_t or (k_bin_build2's prologue inside a call, BuildPrologue::
+// idx_narrow) int32_t; flag and ids fit either
+template <bool FLAG_ONLY, class IDX>
 __device__ __forceinline__ void compact_tiles(const int64_t *__restrict__ multiplicity,
-                                              const int64_t *__restrict__ idx, int64_t flag,
+                                              const IDX *__restrict__ idx, int64_t flag,
                                               int64_t length, int tile, int tile_end, int lane,
                                               bool *dead, int64_t *val) {
   int64_t v[COMPACT_UNROLL], n[COMPACT_UNROLL];
@@ -691,7 +698,7 @@ __device__ __forceinline__ void compact_tiles(const int64_t *__restrict__ multip
   for (int u = 0; u < COMPACT_UNROLL; ++u) {
     const int64_t i = (int64_t)(tile + u) * SDM_WAVE + lane;
     in[u] = tile + u < tile_end && i < length;
-    v[u] = in[u] ? idx[i] : flag;
+    v[u] = in[u] ? (int64_t)idx[i] : flag;
   }
 #pragma unroll
   for (int u = 0; u < COMPACT_UNROLL; ++u)
@@ -736,9 +743,9 @@ __device__ __forceinline__ void compact_epilogue(const CompactEpilogue &E,
 // with a healthy state and only flags positions), so the random gather of multiplicities is skipped
 // the compaction proper, by every workgroup of the grid (all resident; at most COMPACT_MAX_GROUPS);
 // false: a grid barrier timed out (fctl[7] = 2).  *new_length: the length every workgroup computed
-template <bool FLAG_ONLY>
+template <bool FLAG_ONLY, class IDX = int64_t>
 __device__ __forceinline__ bool
-compact_run(const int64_t *__restrict__ multiplicity, int64_t *__restrict__ idx, int64_t flag,
+compact_run(const int64_t *__restrict__ multiplicity, IDX *__restrict__ idx, int64_t flag,
             int64_t *__restrict__ fctl, int32_t *__restrict__ wave_dead, int n_tiles,
             int64_t *__restrict__ ctl, int32_t *__restrict__ holes, int64_t *__restrict__ fillers,
             int64_t *__restrict__ cell_start_single, unsigned int *__restrict__ bar,
@@ -762,7 +769,7 @@ compact_run(const int64_t *__restrict__ multiplicity, int64_t *__restrict__ idx,
     int count = 0;
     for (int tile = tile0; tile < tile1; tile += COMPACT_UNROLL) {
       bool dead[COMPACT_UNROLL];
-      compact_tiles<FLAG_ONLY>(multiplicity, idx, flag, length, tile, tile1, lane, dead, nullptr);
+      compact_tiles<FLAG_ONLY, IDX>(multiplicity, idx, flag, length, tile, tile1, lane, dead, nullptr);
 #pragma unroll
       for (int u = 0; u < COMPACT_UNROLL; ++u) count += __popcll(__ballot(dead[u]));
     }
@@ -816,7 +823,7 @@ compact_run(const int64_t *__restrict__ multiplicity, int64_t *__restrict__ idx,
     for (int tile = tile0; tile < tile1; tile += COMPACT_UNROLL) {
       bool dead[COMPACT_UNROLL];
       int64_t val[COMPACT_UNROLL];
-      compact_tiles<FLAG_ONLY>(multiplicity, idx, flag, length, tile, tile1, lane, dead, val);
+      compact_tiles<FLAG_ONLY, IDX>(multiplicity, idx, flag, length, tile, tile1, lane, dead, val);
 #pragma unroll
       for (int u = 0; u < COMPACT_UNROLL; ++u) {
         const int64_t i = (int64_t)(tile + u) * SDM_WAVE + lane;
@@ -841,8 +848,8 @@ compact_run(const int64_t *__restrict__ multiplicity, int64_t *__restrict__ idx,
     const int64_t n_holes = ((volatile int64_t *)ctl)[2];
     for (int64_t t = (int64_t)blockIdx.x * COMPACT_THREADS + threadIdx.x; t < length - new_len;
          t += (int64_t)gridDim.x * COMPACT_THREADS) {
-      idx[new_len + t] = flag;
-      if (t < n_holes) idx[((volatile int32_t *)holes)[t]] = ((volatile int64_t *)fillers)[t];
+      idx[new_len + t] = (IDX)flag;
+      if (t < n_holes) idx[((volatile int32_t *)holes)[t]] = (IDX)((volatile int64_t *)fillers)[t];
     }
   }
   BARRIER_OR_FAIL(3)
@@ -969,7 +976,7 @@ __device__ __forceinline__ void
 bin_build_chain(int32_t *__restrict__ lds, uint32_t *__restrict__ first,
                 uint32_t *__restrict__ tsucc, const uint32_t *__restrict__ events,
                 const int32_t *__restrict__ toff, int n_bins, int n_tiles, int ev_tile,
-                const int64_t *__restrict__ idx0, int64_t length, int64_t base,
+                const int64_t *__restrict__ idx0, bool idx_narrow, int64_t length, int64_t base,
                 const int32_t *loc, int32_t *links, uint32_t *ssucc) {
   static_assert(BIN_POS == 4 * BIN_THREADS, "a thread owns four consecutive positions");
   constexpr int SLOTS = 5;
@@ -1000,11 +1007,25 @@ bin_build_chain(int32_t *__restrict__ lds, uint32_t *__restrict__ first,
   // what the records need from memory besides the hits, requested now, used after the placing.
   // A thread takes the positions tid + k * BIN_THREADS here: four consecutive ones (two 16-byte
   // loads of idx0, one of loc) made this phase 0.6 us longer (profiles/README.md, round 8)
+  // (round 9: inside a call the ids come as 32 bits - the pair kernel of the previous step wrote
+  // them so; uniform over the grid)
   int32_t id_v[4], loc_v[4];
+  if (NARROW_IDX && idx_narrow) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int64_t p = base + threadIdx.x + k * BIN_THREADS;
+      id_v[k] = p < length ? ((const int32_t *)idx0)[p] : 0;
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int64_t p = base + threadIdx.x + k * BIN_THREADS;
+      id_v[k] = p < length ? (int32_t)idx0[p] : 0;
+    }
+  }
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const int64_t p = base + threadIdx.x + k * BIN_THREADS;
-    id_v[k] = p < length ? (int32_t)idx0[p] : 0;
     loc_v[k] = p < length ? loc[p] : -1;
   }
   BIN_MARK(9);
@@ -1128,10 +1149,16 @@ k_bin_build2(void *__restrict__ rec_out, int32_t *__restrict__ ovf_head,
   if (P.compact.fctl && P.compact.fctl[FCTL_HEALTHY] == 0) {
     const CompactEpilogue none = {nullptr, nullptr, nullptr, 0, nullptr, 0, 0};
     const SortPrologue &C = P.compact;
-    if (!compact_run<true>(C.multiplicity, C.idx, C.flag, C.fctl, C.wave_dead, C.n_tiles, C.ctl,
-                           C.holes, C.fillers, C.cell_start_single, C.bar, none, &length,
-                           (int *)smem))
-      return;
+    // (the permutation as the pair kernel left it: 32-bit ids inside a call - compacted as they
+    // stand; widening them first would be a pass of its own and a grid barrier more)
+    const bool through = (NARROW_IDX && P.idx_narrow)
+        ? compact_run<true, int32_t>(C.multiplicity, (int32_t *)C.idx, C.flag, C.fctl, C.wave_dead,
+                                     C.n_tiles, C.ctl, C.holes, C.fillers, C.cell_start_single,
+                                     C.bar, none, &length, (int *)smem)
+        : compact_run<true, int64_t>(C.multiplicity, C.idx, C.flag, C.fctl, C.wave_dead, C.n_tiles,
+                                     C.ctl, C.holes, C.fillers, C.cell_start_single, C.bar, none,
+                                     &length, (int *)smem);
+    if (!through) return;
     __syncthreads();
     bin_sort_body<true>(smem, P.events, P.toff, P.jarr, P.loc, n_bins, nullptr, nullptr, 1, length,
                         length, P.s_off, P.inc, P.tab, nullptr, P.aff);
@@ -1149,7 +1176,8 @@ k_bin_build2(void *__restrict__ rec_out, int32_t *__restrict__ ovf_head,
     // (first = the record buffer, tsucc = ovf_head; the overflow links have scratch of their own:
     // ovf_next is the ssucc table here)
     bin_build_chain((int32_t *)smem, (uint32_t *)rec_out, (uint32_t *)ovf_head, events, toff,
-                    n_bins, n_tiles, ev_tile, idx0, length, base, P.loc, P.chain_links, P.ssucc);
+                    n_bins, n_tiles, ev_tile, idx0, P.idx_narrow != 0, length, base, P.loc,
+                    P.chain_links, P.ssucc);
     return;
   }
   const int bin = blockIdx.x;
@@ -1192,7 +1220,8 @@ k_bin_build2(void *__restrict__ rec_out, int32_t *__restrict__ ovf_head,
 #pragma unroll
   for (int k = 0; k < PER_POS; ++k) {
     const int64_t p = base + threadIdx.x + k * BIN_THREADS;
-    id_v[k] = p < length ? idx0[p] : 0;
+    id_v[k] = p >= length ? 0
+              : (NARROW_IDX && P.idx_narrow) ? (int64_t)((const int32_t *)idx0)[p] : idx0[p];
     j_v[k] = p < length ? jarr[p] : -1;
   }
   BIN_MARK(9);

@@ -83,6 +83,12 @@ __device__ __forceinline__ void sort_store16(void *buf, int64_t at, sort_v4i v) 
 #ifndef BUILD_STORE
 #define BUILD_STORE 1
 #endif
+// ---- the permutation between two steps of one call as 32-bit ids (round 9; fused.hip: a pair
+// kernel that sorts ahead writes them, index.hip: the next build and its compaction read them).
+// -DNARROW_IDX=0 keeps int64_t at compile time, SDM_OPT_NARROW_STEP = 1 at run time
+#ifndef NARROW_IDX
+#define NARROW_IDX 1
+#endif
 // dynamic LDS of the tile sort: bin starts (n_bins + 1) and counts (n_bins), rounded up to whole
 // 16 bytes, then the tile's packed events
 __host__ __device__ constexpr int bin_sort_head_words(int n_bins) { return (2 * n_bins + 2 + 3) & ~3; }
