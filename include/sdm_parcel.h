@@ -99,6 +99,10 @@ int sdm_parcel_run(sdm_ctx *ctx, const sdm_parcel_cfg *cfg, int64_t n_steps, int
 /* the `steps_per_launch` a cfg with 0 gets */
 #define SDM_PARCEL_STEPS_PER_LAUNCH 16
 
+/* The same call with statistical moments and a size spectrum of every parcel's droplets evaluated
+ * after every step, inside the same loop: sdm_parcel_run_diag of sdm_parcel_diag.h (a header of
+ * its own, so that an implementation of this one need not implement it). */
+
 #ifdef __cplusplus
 }
 #endif

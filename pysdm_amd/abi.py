@@ -41,6 +41,8 @@ INITIALISATION_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include",
                                           "sdm_initialisation.h")
 # and the adiabatic-parcel path (whole ascents of ensembles of parcels)
 PARCEL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "sdm_parcel.h")
+# and the parcel's diagnostics (moments and a size spectrum per step)
+PARCEL_DIAG_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "sdm_parcel_diag.h")
 # SDM_HIP_LIB: another build of the same library (tuning variants); still no fallback
 HIP_LIB_PATH = os.environ.get("SDM_HIP_LIB") or os.path.join(_HERE, "libsdm_hip.so")
 
@@ -185,6 +187,34 @@ class ParcelState(ctypes.Structure):  # == sdm_parcel_state
 
 class ParcelProfile(ctypes.Structure):  # == sdm_parcel_profile
     _fields_ = [(name, c_ptr) for name in PARCEL_PROFILE_FIELDS]
+
+
+# include/sdm_parcel_diag.h: SDM_PARCEL_MAX_*, SDM_PARCEL_ATTR_*, SDM_PARCEL_FILTER_*
+PARCEL_MAX_MOMENTS, PARCEL_MAX_BINS = 16, 256
+PARCEL_ATTRS = {"water mass": 0, "volume": 1, "radius": 2, "dry volume": 3, "dry radius": 4}
+PARCEL_FILTERS = {"water mass": 0, "signed water mass": 0, "volume": 1, "dry volume": 2,
+                  "wet to critical volume ratio": 3}
+PARCEL_DIAG_FIELDS = ("moment_0", "moments", "spectrum", "dv")
+
+
+class ParcelMomentRequest(ctypes.Structure):  # == sdm_parcel_moment_request
+    _fields_ = [
+        ("attr", ctypes.c_int32), ("filter_attr", ctypes.c_int32), ("rank", c_f64),
+        ("min_x", c_f64), ("max_x", c_f64), ("skip_division_by_m0", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
+class ParcelRequests(ctypes.Structure):  # == sdm_parcel_requests
+    _fields_ = [
+        ("n_moments", ctypes.c_int32), ("n_bins", ctypes.c_int32), ("bin_attr", ctypes.c_int32),
+        ("reserved", ctypes.c_int32), ("moment", ParcelMomentRequest * PARCEL_MAX_MOMENTS),
+        ("edges", c_f64 * (PARCEL_MAX_BINS + 1)),
+    ]
+
+
+class ParcelDiag(ctypes.Structure):  # == sdm_parcel_diag
+    _fields_ = [(name, c_ptr) for name in PARCEL_DIAG_FIELDS]
 
 
 class RelaxedVelocityCfg(ctypes.Structure):  # == sdm_relaxed_velocity_cfg
@@ -363,6 +393,7 @@ _seeding_library = None
 _relaxed_velocity_library = None
 _initialisation_library = None
 _parcel_library = None
+_parcel_diag_library = None
 
 
 def hip_library():
@@ -452,6 +483,15 @@ def parcel_library():
         _parcel_library = Library(HIP_LIB_PATH, "the HIP kernels of pysdm_amd",
                                   header=PARCEL_HEADER_PATH)
     return _parcel_library
+
+
+def parcel_diag_library():
+    """libsdm_hip.so bound to include/sdm_parcel_diag.h (same file, same contexts)"""
+    global _parcel_diag_library  # pylint: disable=global-statement
+    if _parcel_diag_library is None:
+        _parcel_diag_library = Library(HIP_LIB_PATH, "the HIP kernels of pysdm_amd",
+                                       header=PARCEL_DIAG_HEADER_PATH)
+    return _parcel_diag_library
 
 
 def pcg64_state_inc(seed):

@@ -119,6 +119,9 @@ struct sdm_ctx {
   int64_t *parcel_identity;
   double *parcel_backup;
   int64_t parcel_rows;
+  // the request table of the current sdm_parcel_run_diag / sdm_parcel_diagnose call in device
+  // memory (one sdm_parcel_requests, allocated at the first such call)
+  void *parcel_requests;
   // device control words for fine-grained calls (int64[16]; word 6: dt_left[0] of an adaptive
   // single cell for the next sub-step, fused.hip; 8: a length; 10-11: adaptive_end; 12-15: barrier)
   int64_t *dscal;

@@ -167,6 +167,17 @@ __global__ __launch_bounds__(COND_CB) void k_parcel(ParcelArgs<DefaultFormulae> 
   parcel_steps<DefaultFormulae>(a);
 }
 
+// include/sdm_parcel_diag.h: the same loop with the request table evaluated after every step, and
+// the table on given columns
+__global__ __launch_bounds__(COND_CB) void k_parcel_d(ParcelArgs<DefaultFormulae> a,
+                                                      ParcelDiag d) {
+  parcel_steps<DefaultFormulae, true>(a, &d);
+}
+__global__ __launch_bounds__(COND_CB) void k_parcel_diagnose(
+    ParcelDiagnoseArgs<DefaultFormulae> a) {
+  parcel_diagnose_cells<DefaultFormulae>(a);
+}
+
 // ---- ambient methods (pm.py) ---------------------------------------------------------------------
 __global__ void k_temperature_pressure_rh(const double *rhod, const double *thd, const double *qv,
                                           double *T, double *p, double *RH, int64_t n, Kc k) {
@@ -241,7 +252,23 @@ int sdm_parcel_launch_default(sdm_ctx *ctx, const ParcelCall &call) {
   ParcelArgs<DefaultFormulae> a;
   SDM_PARCEL_FILL_ARGS(a, call);
   a.c.k = consts_of(call.consts);
-  hipLaunchKernelGGL(k_parcel, dim3((unsigned)call.n_parcel), dim3(COND_CB), 0, ctx->stream, a);
+  if (call.requests) {
+    const ParcelDiag d{call.requests, call.diag};
+    hipLaunchKernelGGL(k_parcel_d, dim3((unsigned)call.n_parcel), dim3(COND_CB), 0, ctx->stream,
+                       a, d);
+  } else {
+    hipLaunchKernelGGL(k_parcel, dim3((unsigned)call.n_parcel), dim3(COND_CB), 0, ctx->stream, a);
+  }
+  LAUNCH_CHECK();
+  return SDM_OK;
+}
+
+int sdm_parcel_diagnose_default(sdm_ctx *ctx, const ParcelDiagnoseCall &call) {
+  ParcelDiagnoseArgs<DefaultFormulae> a;
+  a.k = consts_of(call.consts);
+  SDM_PARCEL_FILL_DIAGNOSE_ARGS(a, call);
+  hipLaunchKernelGGL(k_parcel_diagnose, dim3((unsigned)call.n_parcel), dim3(COND_CB), 0,
+                     ctx->stream, a);
   LAUNCH_CHECK();
   return SDM_OK;
 }

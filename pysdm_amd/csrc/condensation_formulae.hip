@@ -179,6 +179,17 @@ __global__ __launch_bounds__(COND_CB) void k_parcel_f(ParcelArgs<GeneralFormulae
   parcel_steps<GeneralFormulae>(a);
 }
 
+// include/sdm_parcel_diag.h: the same loop with the request table evaluated after every step, and
+// the table on given columns
+__global__ __launch_bounds__(COND_CB) void k_parcel_f_d(ParcelArgs<GeneralFormulae> a,
+                                                        ParcelDiag d) {
+  parcel_steps<GeneralFormulae, true>(a, &d);
+}
+__global__ __launch_bounds__(COND_CB) void k_parcel_diagnose_f(
+    ParcelDiagnoseArgs<GeneralFormulae> a) {
+  parcel_diagnose_cells<GeneralFormulae>(a);
+}
+
 // ---- ambient methods (pm.py) ---------------------------------------------------------------------
 __global__ void k_temperature_pressure_rh_f(const double *rhod, const double *thd,
                                             const double *qv, double *T, double *p, double *RH,
@@ -259,7 +270,30 @@ int sdm_parcel_launch_general(sdm_ctx *ctx, const ParcelCall &call,
   a.c.k.reynolds_number = nullptr;
   a.c.k.vdry = call.vdry;
   a.c.k.air_density = a.c.k.air_dynamic_viscosity = nullptr;
-  hipLaunchKernelGGL(k_parcel_f, dim3((unsigned)call.n_parcel), dim3(COND_CB), 0, ctx->stream, a);
+  if (call.requests) {
+    const ParcelDiag d{call.requests, call.diag};
+    hipLaunchKernelGGL(k_parcel_f_d, dim3((unsigned)call.n_parcel), dim3(COND_CB), 0, ctx->stream,
+                       a, d);
+  } else {
+    hipLaunchKernelGGL(k_parcel_f, dim3((unsigned)call.n_parcel), dim3(COND_CB), 0, ctx->stream,
+                       a);
+  }
+  LAUNCH_CHECK();
+  return SDM_OK;
+}
+
+int sdm_parcel_diagnose_general(sdm_ctx *ctx, const ParcelDiagnoseCall &call,
+                                const sdm_cond_formulae *formulae) {
+  ParcelDiagnoseArgs<GeneralFormulae> a;
+  ARG_TRY(formulae && formulae_of(call.consts, formulae, &a.k.f));
+  ARG_TRY(formulae->option[SDM_COND_OPT_SURFACE_TENSION] == SDM_COND_SGM_CONSTANT || call.f_org);
+  a.k.f_org = call.f_org;
+  a.k.reynolds_number = nullptr;
+  a.k.vdry = call.vdry;
+  a.k.air_density = a.k.air_dynamic_viscosity = nullptr;
+  SDM_PARCEL_FILL_DIAGNOSE_ARGS(a, call);
+  hipLaunchKernelGGL(k_parcel_diagnose_f, dim3((unsigned)call.n_parcel), dim3(COND_CB), 0,
+                     ctx->stream, a);
   LAUNCH_CHECK();
   return SDM_OK;
 }

@@ -3,6 +3,8 @@
 // are the instantiations of parcel_solver.h (where their design is described) next to those of the
 // condensation solver: k_parcel in condensation.hip (PySDM's default formulae), k_parcel_f in
 // condensation_formulae.hip (a descriptor); this file reaches both through their launchers.
+// Likewise include/sdm_parcel_diag.h: its request table is checked here and copied to device
+// memory once per call; k_parcel_d / k_parcel_f_d and k_parcel_diagnose(_f) read it there.
 //
 // A call of n_steps enqueues ceil(n_steps / steps_per_launch) launches back to back on the
 // context's stream, without synchronising between them: one launch stays short on a shared card,
@@ -32,6 +34,53 @@ int reserve_rows(sdm_ctx *ctx, int64_t n_sd) {
   return sdm_identity_index(ctx, ctx->parcel_identity, want);
 }
 
+// every parcel has rows, and they lie within the columns: the kernels index by these words
+int check_starts(sdm_ctx *ctx, const int64_t *parcel_start, int64_t n_parcel, int64_t n_sd) {
+  std::vector<int64_t> starts((size_t)n_parcel + 1);
+  HIP_TRY(hipMemcpyAsync(starts.data(), parcel_start, starts.size() * sizeof(int64_t),
+                         hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  ARG_TRY(starts[0] >= 0 && starts[(size_t)n_parcel] <= n_sd);
+  for (int64_t c = 0; c < n_parcel; ++c)
+    if (starts[(size_t)c + 1] <= starts[(size_t)c]) {
+      sdm_set_error("sdm_parcel_run: parcel %lld has no rows", (long long)c);
+      return SDM_E_ARG;
+    }
+  return SDM_OK;
+}
+
+// the refusals of include/sdm_parcel_diag.h (comparisons written so that a NaN fails them)
+int check_requests(const sdm_parcel_requests *rq) {
+  ARG_TRY(rq->n_moments >= 0 && rq->n_moments <= SDM_PARCEL_MAX_MOMENTS);
+  ARG_TRY(rq->n_bins >= 0 && rq->n_bins <= SDM_PARCEL_MAX_BINS);
+  for (int i = 0; i < rq->n_moments; ++i) {
+    const sdm_parcel_moment_request &m = rq->moment[i];
+    ARG_TRY(m.attr >= 0 && m.attr < SDM_PARCEL_N_ATTRS);
+    ARG_TRY(m.filter_attr >= 0 && m.filter_attr < SDM_PARCEL_N_FILTERS);
+    ARG_TRY(m.min_x <= m.max_x);
+    ARG_TRY(m.rank == m.rank);
+  }
+  if (rq->n_bins > 0) {
+    ARG_TRY(rq->bin_attr >= 0 && rq->bin_attr < SDM_PARCEL_N_FILTERS);
+    for (int b = 0; b < rq->n_bins; ++b) ARG_TRY(rq->edges[b] < rq->edges[b + 1]);
+  }
+  return SDM_OK;
+}
+
+// the table to device memory, behind whatever still reads the previous one on the stream; the
+// caller synchronises the stream before it returns (the source is the caller's host struct)
+int upload_requests(sdm_ctx *ctx, const sdm_parcel_requests *rq) {
+  if (!ctx->parcel_requests)
+    HIP_TRY(hipMalloc(&ctx->parcel_requests, sizeof(sdm_parcel_requests)));
+  HIP_TRY(hipMemcpyAsync(ctx->parcel_requests, rq, sizeof(sdm_parcel_requests),
+                         hipMemcpyHostToDevice, ctx->stream));
+  return SDM_OK;
+}
+
+bool wants_output(const sdm_parcel_diag *diag) {
+  return diag && (diag->moment_0 || diag->moments || diag->spectrum || diag->dv);
+}
+
 }  // namespace
 
 extern "C" int sdm_parcel_run(sdm_ctx *ctx, const sdm_parcel_cfg *cfg, int64_t n_steps,
@@ -41,6 +90,20 @@ extern "C" int sdm_parcel_run(sdm_ctx *ctx, const sdm_parcel_cfg *cfg, int64_t n
                               double *v_cr, const sdm_parcel_state *state, const double *w_mid,
                               const sdm_parcel_profile *profile, const double consts[34],
                               const sdm_cond_formulae *formulae) {
+  return sdm_parcel_run_diag(ctx, cfg, n_steps, n_parcel, n_sd, parcel_start, water_mass,
+                             multiplicity, vdry, kappa, f_org, v_cr, state, w_mid, profile, consts,
+                             formulae, nullptr, nullptr);
+}
+
+extern "C" int sdm_parcel_run_diag(sdm_ctx *ctx, const sdm_parcel_cfg *cfg, int64_t n_steps,
+                                   int64_t n_parcel, int64_t n_sd, const int64_t *parcel_start,
+                                   double *water_mass, const int64_t *multiplicity,
+                                   const double *vdry, const double *kappa, const double *f_org,
+                                   double *v_cr, const sdm_parcel_state *state,
+                                   const double *w_mid, const sdm_parcel_profile *profile,
+                                   const double consts[34], const sdm_cond_formulae *formulae,
+                                   const sdm_parcel_requests *requests,
+                                   const sdm_parcel_diag *diag) {
   ARG_TRY(ctx && cfg && consts && state);
   ARG_TRY(n_steps >= 0 && n_parcel >= 0 && n_sd >= 0 && n_parcel <= 0x7fffffff);
   ARG_TRY(cfg->multiplier >= 1 && cfg->fuse >= 0 && cfg->max_iters >= 0 && cfg->dt > 0);
@@ -48,24 +111,24 @@ extern "C" int sdm_parcel_run(sdm_ctx *ctx, const sdm_parcel_cfg *cfg, int64_t n
   ARG_TRY(cfg->steps_per_launch >= 0);
   if (formulae)  // (the general launcher checks the rest of the descriptor)
     ARG_TRY(formulae->option[SDM_COND_OPT_VENTILATION] == SDM_COND_VENT_NEGLECT);
+  const bool with_diag = wants_output(diag);  // otherwise: the kernels of sdm_parcel_run
+  if (requests) {
+    const int checked = check_requests(requests);
+    if (checked != SDM_OK) return checked;
+  }
+  ARG_TRY(!with_diag || requests);
   if (n_parcel == 0 || n_steps == 0) return SDM_OK;
   ARG_TRY(parcel_start && water_mass && multiplicity && vdry && kappa && v_cr && w_mid);
   ARG_TRY(state->z && state->rhod && state->thd && state->qv && state->T && state->p &&
           state->RH && state->qv_prev && state->mass_of_dry_air && state->n_substeps &&
           state->n_activating && state->n_deactivating && state->n_ripening && state->RH_max &&
           state->steps_done && state->failed_step);
-  {  // every parcel has rows, and they lie within the columns: the kernels index by these words
-    std::vector<int64_t> starts((size_t)n_parcel + 1);
-    HIP_TRY(hipMemcpyAsync(starts.data(), parcel_start, starts.size() * sizeof(int64_t),
-                           hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    ARG_TRY(starts[0] >= 0 && starts[(size_t)n_parcel] <= n_sd);
-    for (int64_t c = 0; c < n_parcel; ++c)
-      if (starts[(size_t)c + 1] <= starts[(size_t)c]) {
-        sdm_set_error("sdm_parcel_run: parcel %lld has no rows", (long long)c);
-        return SDM_E_ARG;
-      }
+  if (with_diag) {
+    const int uploaded = upload_requests(ctx, requests);
+    if (uploaded != SDM_OK) return uploaded;
   }
+  const int starts_ok = check_starts(ctx, parcel_start, n_parcel, n_sd);  // (synchronises)
+  if (starts_ok != SDM_OK) return starts_ok;
   const int rc = reserve_rows(ctx, n_sd);
   if (rc != SDM_OK) return rc;
 
@@ -87,6 +150,9 @@ extern "C" int sdm_parcel_run(sdm_ctx *ctx, const sdm_parcel_cfg *cfg, int64_t n
   call.state = *state;
   if (profile) call.profile = *profile;
   else memset(&call.profile, 0, sizeof(call.profile));
+  call.requests = with_diag ? (const sdm_parcel_requests *)ctx->parcel_requests : nullptr;
+  if (with_diag) call.diag = *diag;
+  else memset(&call.diag, 0, sizeof(call.diag));
   const int64_t per_launch =
       cfg->steps_per_launch > 0 ? cfg->steps_per_launch : SDM_PARCEL_STEPS_PER_LAUNCH;
   for (int64_t k0 = 0; k0 < n_steps; k0 += per_launch) {
@@ -97,4 +163,39 @@ extern "C" int sdm_parcel_run(sdm_ctx *ctx, const sdm_parcel_cfg *cfg, int64_t n
     if (launched != SDM_OK) return launched;
   }
   return SDM_OK;
+}
+
+extern "C" int sdm_parcel_diagnose(sdm_ctx *ctx, int64_t n_parcel, int64_t n_sd,
+                                   const int64_t *parcel_start, const double *water_mass,
+                                   const int64_t *multiplicity, const double *vdry,
+                                   const double *kappa, const double *f_org, const double *T,
+                                   const double consts[34], const sdm_cond_formulae *formulae,
+                                   const sdm_parcel_requests *requests,
+                                   const sdm_parcel_diag *diag) {
+  ARG_TRY(ctx && consts && requests && diag);
+  ARG_TRY(n_parcel >= 0 && n_sd >= 0 && n_parcel <= 0x7fffffff);
+  const int checked = check_requests(requests);
+  if (checked != SDM_OK) return checked;
+  if (n_parcel == 0) return SDM_OK;
+  ARG_TRY(parcel_start && water_mass && multiplicity && vdry && kappa && T);
+  const int uploaded = upload_requests(ctx, requests);
+  if (uploaded != SDM_OK) return uploaded;
+  const int starts_ok = check_starts(ctx, parcel_start, n_parcel, n_sd);  // (synchronises)
+  if (starts_ok != SDM_OK) return starts_ok;
+  ParcelDiagnoseCall call;
+  call.n_parcel = n_parcel;
+  call.n_sd = n_sd;
+  call.parcel_start = parcel_start;
+  call.multiplicity = multiplicity;
+  call.water_mass = water_mass;
+  call.vdry = vdry;
+  call.kappa = kappa;
+  call.f_org = f_org;
+  call.T = T;
+  call.consts = consts;
+  call.requests = (const sdm_parcel_requests *)ctx->parcel_requests;
+  call.diag = *diag;
+  call.diag.dv = nullptr;
+  return formulae ? sdm_parcel_diagnose_general(ctx, call, formulae)
+                  : sdm_parcel_diagnose_default(ctx, call);
 }

@@ -29,10 +29,22 @@
 //   lv                     the latent heat of vapourisation
 //   critical_volume        the body of k_critical_volume(_f) for one row
 //   Rv, Rd, c_pv           the constants the hydrostatics reads (c_pd, rho_w are there already)
+//
+// The diagnostics (include/sdm_parcel_diag.h, where the arithmetic and the shape of the sums are
+// written out): parcel_diagnose evaluates a request table for one parcel in one pass over its
+// rows.  It runs in the step loop of `parcel_steps<P, true>` (k_parcel_d, k_parcel_f_d) after
+// cs.write_back(), where every row's mass was last written by the lane that reads it here, and in
+// k_parcel_diagnose(_f), the stage kernel.  parcel_steps<P, false> is the code it was before:
+// k_parcel and k_parcel_f do not change.  Per lane the pass keeps one partial sum per request in
+// registers (the solver's register cache is dead by then: cs.init() refills it every step); the
+// 256 partials of four sums at a time meet in 8 KiB of LDS (strides 128 and 64 cross the waves),
+// the strides from 32 down are wave shuffles in wave 0.  The spectrum is counted with 64-bit LDS
+// atomics on 2 KiB, its edges sit beside them (2 KiB).  12.1 KiB of LDS beyond the solver's.
 #ifndef SDM_PARCEL_SOLVER_H
 #define SDM_PARCEL_SOLVER_H
 #include "condensation_solver.h"
-#include "../../include/sdm_parcel.h"
+#include "physics.h"
+#include "../../include/sdm_parcel_diag.h"
 
 // one sdm_parcel_run call as the launchers take it (host struct; pointers are device pointers)
 struct ParcelCall {
@@ -44,11 +56,25 @@ struct ParcelCall {
   sdm_parcel_state state;
   sdm_parcel_profile profile;
   int64_t k0, k_count;  // the steps of this launch: rows k0 .. k0 + k_count of w_mid / the profile
+  // sdm_parcel_run_diag: the table in device memory (nullptr: the kernels without diagnostics)
+  const sdm_parcel_requests *requests;
+  sdm_parcel_diag diag;
+};
+// one sdm_parcel_diagnose call (pointers are device pointers, `requests` included)
+struct ParcelDiagnoseCall {
+  int64_t n_parcel, n_sd;
+  const int64_t *parcel_start, *multiplicity;
+  const double *water_mass, *vdry, *kappa, *f_org, *T, *consts;
+  const sdm_parcel_requests *requests;
+  sdm_parcel_diag diag;
 };
 // condensation.hip / condensation_formulae.hip: one launch of the default / general kernel
 int sdm_parcel_launch_default(sdm_ctx *ctx, const ParcelCall &call);
 int sdm_parcel_launch_general(sdm_ctx *ctx, const ParcelCall &call,
                               const sdm_cond_formulae *formulae);
+int sdm_parcel_diagnose_default(sdm_ctx *ctx, const ParcelDiagnoseCall &call);
+int sdm_parcel_diagnose_general(sdm_ctx *ctx, const ParcelDiagnoseCall &call,
+                                const sdm_cond_formulae *formulae);
 
 #ifdef __HIPCC__
 namespace {
@@ -66,13 +92,170 @@ struct ParcelArgs {
   double dt, g_std;
 };
 
+// what the kernels with diagnostics take beside ParcelArgs<P>
+struct ParcelDiag {
+  const sdm_parcel_requests *req;  // device memory
+  sdm_parcel_diag out;
+};
+
+template <class P>
+struct ParcelDiagnoseArgs {
+  typename P::K k;
+  int64_t n_parcel, n_sd;
+  const int64_t *parcel_start, *multiplicity;
+  const double *water_mass, *vdry, *kappa, *T;
+  ParcelDiag d;
+};
+
+#define DIAG_ROUND 4  // sums reduced at a time: moment_0 and moments of two requests
+
+// the LDS of one workgroup's diagnostics (declared where this is inlined: once per kernel)
+struct DiagLds {
+  double *red;               // DIAG_ROUND x COND_CB partials
+  unsigned long long *bins;  // SDM_PARCEL_MAX_BINS counts
+  double *edges;             // SDM_PARCEL_MAX_BINS + 1
+};
+DF void attach_diag_lds(DiagLds &l) {
+  __shared__ double s_red[DIAG_ROUND * COND_CB];
+  __shared__ unsigned long long s_bins[SDM_PARCEL_MAX_BINS];
+  __shared__ double s_edges[SDM_PARCEL_MAX_BINS + 1];
+  l.red = s_red;
+  l.bins = s_bins;
+  l.edges = s_edges;
+}
+
+DF double diag_power(double x, double rank) {
+  return rank == 0 ? 1.0 : (rank == 1 ? x : sdm_pow(x, rank));
+}
+
+// include/sdm_parcel_diag.h for one parcel: rows row0 .. row0 + n at temperature T; out_* point at
+// the parcel's row of the outputs (or are nullptr).  Every lane of the workgroup calls it; the
+// table was checked on the host (counts within the maxima, enums known).
+template <class P>
+DF void parcel_diagnose(const typename P::K &k, const sdm_parcel_requests *rq, const DiagLds &l,
+                        int64_t row0, int64_t n, double T, const double *water_mass,
+                        const int64_t *multiplicity, const double *vdry, const double *kappa,
+                        double *out_m0, double *out_m, double *out_spectrum, int tid) {
+  const int nm = rq->n_moments, nb = rq->n_bins, bin_attr = rq->bin_attr;
+  bool need_r = false, need_rd = false;  // the derived attributes some request reads (uniform)
+  bool need_ratio = nb > 0 && bin_attr == SDM_PARCEL_FILTER_VOLUME_RATIO;
+  for (int i = 0; i < nm; ++i) {
+    need_r = need_r || rq->moment[i].attr == SDM_PARCEL_ATTR_RADIUS;
+    need_rd = need_rd || rq->moment[i].attr == SDM_PARCEL_ATTR_DRY_RADIUS;
+    need_ratio = need_ratio || rq->moment[i].filter_attr == SDM_PARCEL_FILTER_VOLUME_RATIO;
+  }
+  __syncthreads();  // the previous evaluation's reads of this LDS are over; lane 0's T is in LDS
+  for (int b = tid; b < nb; b += COND_CB) l.bins[b] = 0;
+  for (int b = tid; b <= nb; b += COND_CB) l.edges[b] = rq->edges[b];
+  __syncthreads();
+  const double rho_w = P::rho_w(k), inv_pi_4_3 = 1 / P::pi_4_3(k);
+  double acc_0[SDM_PARCEL_MAX_MOMENTS], acc_m[SDM_PARCEL_MAX_MOMENTS];
+#pragma unroll
+  for (int u = 0; u < SDM_PARCEL_MAX_MOMENTS; ++u) acc_0[u] = acc_m[u] = 0.0;
+  for (int64_t q = tid; q < n; q += COND_CB) {
+    const int64_t row = row0 + q;
+    const int64_t mult = multiplicity[row];
+    const double m = water_mass[row], vd = vdry[row], nn = (double)mult;
+    const double v = volume_of_mass(m, rho_w);
+    const double r = need_r ? radius_of_volume(v, inv_pi_4_3) : 0.0;
+    const double rd = need_rd ? radius_of_volume(vd, inv_pi_4_3) : 0.0;
+    const double ratio = need_ratio ? v / P::critical_volume(k, row, kappa[row], vd, v, T) : 0.0;
+    const double filters[SDM_PARCEL_N_FILTERS] = {m, v, vd, ratio};
+    const double attrs[SDM_PARCEL_N_ATTRS] = {m, v, r, vd, rd};
+#pragma unroll 1
+    for (int i = 0; i < nm; ++i) {
+      const sdm_parcel_moment_request &mr = rq->moment[i];
+      double f = filters[0], x = attrs[0];
+#pragma unroll
+      for (int u = 1; u < SDM_PARCEL_N_FILTERS; ++u) f = mr.filter_attr == u ? filters[u] : f;
+#pragma unroll
+      for (int u = 1; u < SDM_PARCEL_N_ATTRS; ++u) x = mr.attr == u ? attrs[u] : x;
+      if (mr.min_x <= f && f < mr.max_x) {
+        const double term = nn * diag_power(x, mr.rank);
+#pragma unroll
+        for (int u = 0; u < SDM_PARCEL_MAX_MOMENTS; ++u) {
+          acc_0[u] = u == i ? acc_0[u] + nn : acc_0[u];
+          acc_m[u] = u == i ? acc_m[u] + term : acc_m[u];
+        }
+      }
+    }
+    if (nb > 0) {
+      double f = filters[0];
+#pragma unroll
+      for (int u = 1; u < SDM_PARCEL_N_FILTERS; ++u) f = bin_attr == u ? filters[u] : f;
+      if (l.edges[0] <= f && f < l.edges[nb]) {
+        int lo = 0, hi = nb;  // edges[lo] <= f < edges[hi]
+        while (hi - lo > 1) {
+          const int mid = (lo + hi) >> 1;
+          if (l.edges[mid] <= f) lo = mid;
+          else hi = mid;
+        }
+        atomicAdd(&l.bins[lo], (unsigned long long)mult);
+      }
+    }
+  }
+#pragma unroll
+  for (int r0 = 0; r0 < SDM_PARCEL_MAX_MOMENTS; r0 += DIAG_ROUND / 2) {
+    if (r0 >= nm) break;  // (uniform)
+    if (r0 > 0) __syncthreads();  // wave 0 has read the previous round
+#pragma unroll
+    for (int u = 0; u < DIAG_ROUND / 2; ++u) {
+      l.red[(2 * u) * COND_CB + tid] = acc_0[r0 + u];
+      l.red[(2 * u + 1) * COND_CB + tid] = acc_m[r0 + u];
+    }
+    __syncthreads();
+    if (tid < 64) {
+#pragma unroll
+      for (int u = 0; u < DIAG_ROUND / 2; ++u) {
+        double s[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const double *p = l.red + (2 * u + h) * COND_CB + tid;
+          double part = (p[0] + p[128]) + (p[64] + p[192]);  // strides 128, then 64
+#pragma unroll
+          for (int stride = 32; stride >= 1; stride >>= 1) part += __shfl_down(part, stride, 64);
+          s[h] = part;
+        }
+        const int i = r0 + u;
+        if (tid == 0 && i < nm) {
+          if (out_m0) out_m0[i] = s[0];
+          if (out_m)
+            out_m[i] = rq->moment[i].skip_division_by_m0 ? s[1] : (s[0] != 0 ? s[1] / s[0] : 0.0);
+        }
+      }
+    }
+  }
+  __syncthreads();  // every lane's atomics on the bins are done
+  if (out_spectrum)
+    for (int b = tid; b < nb; b += COND_CB) out_spectrum[b] = (double)l.bins[b];
+}
+
+// the stage kernel of sdm_parcel_diagnose: one workgroup per parcel, striding
+template <class P>
+DF void parcel_diagnose_cells(const ParcelDiagnoseArgs<P> &a) {
+  DiagLds l;
+  attach_diag_lds(l);
+  const int nm = a.d.req->n_moments, nb = a.d.req->n_bins;
+  for (int64_t c = blockIdx.x; c < a.n_parcel; c += gridDim.x) {
+    const int64_t row0 = a.parcel_start[c], n = a.parcel_start[c + 1] - row0;
+    if (row0 < 0 || n <= 0 || row0 + n > a.n_sd) continue;  // (checked on the host too)
+    parcel_diagnose<P>(a.k, a.d.req, l, row0, n, a.T[c], a.water_mass, a.multiplicity, a.vdry,
+                       a.kappa, a.d.out.moment_0 ? a.d.out.moment_0 + c * nm : nullptr,
+                       a.d.out.moments ? a.d.out.moments + c * nm : nullptr,
+                       a.d.out.spectrum ? a.d.out.spectrum + c * nb : nullptr,
+                       (int)threadIdx.x);
+  }
+}
+
 // the slots of the parcel's scalars in LDS
 enum { PS_Z, PS_RHOD, PS_THD, PS_QV, PS_T, PS_P, PS_RH, PS_QV_PREV, PS_PRHOD, PS_PZ, PS_N };
 
-template <class P>
-DF void parcel_steps(const ParcelArgs<P> &a) {
+template <class P, bool DIAG = false>
+DF void parcel_steps(const ParcelArgs<P> &a, const ParcelDiag *d = nullptr) {
   __shared__ double s_par[PS_N];
   __shared__ int64_t s_nsub;
+  DiagLds dl;
+  if constexpr (DIAG) attach_diag_lds(dl);
   const CondArgs<P> &g = a.c;
   const typename P::K &k = g.k;
   const int tid = (int)threadIdx.x;
@@ -176,6 +359,16 @@ DF void parcel_steps(const ParcelArgs<P> &a) {
         if (a.pr.n_deactivating) a.pr.n_deactivating[at] = s.o.n_deactivating;
         if (a.pr.n_ripening) a.pr.n_ripening[at] = s.o.n_ripening;
       }
+      if constexpr (DIAG) {  // the products of the state after the step, at its temperature
+        const int64_t at = (a.k0 + j) * a.n_parcel + c;
+        const int nm = d->req->n_moments, nb = d->req->n_bins;
+        if (tid == 0 && d->out.dv) d->out.dv[at] = dv;
+        __syncthreads();  // lane 0's new T is in LDS
+        parcel_diagnose<P>(k, d->req, dl, row0, n, s_par[PS_T], g.water_mass, g.multiplicity,
+                           g.vdry, g.kappa, d->out.moment_0 ? d->out.moment_0 + at * nm : nullptr,
+                           d->out.moments ? d->out.moments + at * nm : nullptr,
+                           d->out.spectrum ? d->out.spectrum + at * nb : nullptr, tid);
+      }
     }
     if (tid == 0) {  // (lane 0 wrote s_par itself: program order)
       if (failed >= 0) a.st.failed_step[c] = failed;  // (the failed step left s_par as it was)
@@ -240,6 +433,21 @@ DF void parcel_steps(const ParcelArgs<P> &a) {
     (a).n_clamp_hi = cfg__.n_clamp_hi;                                                         \
     (a).dt = cfg__.dt;                                                                         \
     (a).g_std = cfg__.g_std;                                                                   \
+  } while (0)
+
+// the fields of ParcelDiagnoseArgs<P> but `k`
+#define SDM_PARCEL_FILL_DIAGNOSE_ARGS(a, call) \
+  do {                                         \
+    (a).n_parcel = (call).n_parcel;            \
+    (a).n_sd = (call).n_sd;                    \
+    (a).parcel_start = (call).parcel_start;    \
+    (a).multiplicity = (call).multiplicity;    \
+    (a).water_mass = (call).water_mass;        \
+    (a).vdry = (call).vdry;                    \
+    (a).kappa = (call).kappa;                  \
+    (a).T = (call).T;                          \
+    (a).d.req = (call).requests;               \
+    (a).d.out = (call).diag;                   \
   } while (0)
 #endif  // __HIPCC__
 

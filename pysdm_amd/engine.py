@@ -39,6 +39,8 @@ class Engine:
     initialisation_library = None
     # likewise include/sdm_parcel.h
     parcel_library = None
+    # likewise include/sdm_parcel_diag.h
+    parcel_diag_library = None
     # whether the fused collision step of `library` can take the fall velocity from the
     # "relative fall momentum" row; an engine that cannot must refuse, not ignore the request
     fused_momentum_velocity = False
@@ -149,6 +151,13 @@ class Engine:
         self._before_call()
         self.parcel_library.invoke(symbol, self.handle, args)
 
+    def call_parcel_diag(self, symbol, *args):
+        """a symbol of include/sdm_parcel_diag.h"""
+        if self.parcel_diag_library is None:
+            raise NotImplementedError(f"engine `{self.name}` has no parcel-diagnostics library")
+        self._before_call()
+        self.parcel_diag_library.invoke(symbol, self.handle, args)
+
     def _before_call(self):
         pass
 
@@ -186,6 +195,7 @@ class HipEngine(Engine):
         self.relaxed_velocity_library = abi.relaxed_velocity_library()
         self.initialisation_library = abi.initialisation_library()
         self.parcel_library = abi.parcel_library()
+        self.parcel_diag_library = abi.parcel_diag_library()
         self.handle = abi.c_ptr()
         self.library.check(self.library.cdll.sdm_ctx_create(ctypes.byref(self.handle),
                                                             abi.c_int(device_index)))

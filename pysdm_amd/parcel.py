@@ -16,7 +16,10 @@ the critical volume) as engine arrays and runs time steps on one of two routes:
 The time step is the one include/sdm_parcel.h writes out (environments/parcel.py:101-153,
 environments/impl/moist.py:73-100, dynamics/condensation.py:95-131), with the hydrostatics
 ConstantGVapourMixingRatioAndThetaStd; the initial state follows `Parcel.register`
-(parcel.py:51-71).  Products and observers have no place here: `run` returns the profile.
+(parcel.py:51-71).  `run` returns the profile and, with `products=` (pysdm_amd/products.py), the
+products of the state after every step: the fused route evaluates their request table inside the
+kernel's step loop (`sdm_parcel_run_diag`, include/sdm_parcel_diag.h), the stage route with
+`sdm_parcel_diagnose` after each step; `diagnose` gives the products of the current state.
 """
 import numpy as np
 
@@ -25,6 +28,7 @@ from .condensation import (CONSTANT_NAMES, OPTION_ORDER, _option_name, check_for
                            condensation_call, critical_volume_call, is_default,
                            temperature_pressure_rh_call)
 from .engine import FLOAT, INT
+from .products import RequestTable, Rows
 
 HYDROSTATICS = "ConstantGVapourMixingRatioAndThetaStd"
 G_STD = 9.80665  # PySDM/physics/constants_defaults.py: g_std (scipy.constants.g)
@@ -76,11 +80,13 @@ def parcel_cfg(formulae, setup, dt, steps_per_launch=0):
 
 def parcel_call(engine, formulae, cfg, *, n_steps, parcel_start, water_mass, multiplicity,
                 dry_volume, kappa, f_org, critical_volume, state, w_mid, profile=None,
-                descriptor=None, general=False):
+                descriptor=None, general=False, requests=None, diag=None):
     """one `sdm_parcel_run` call with raw engine arrays: `state` / `profile` are dicts of engine
     arrays by the member names of sdm_parcel_state / sdm_parcel_profile (`profile` may be None or
     lack members), `w_mid` an engine array of n_steps x n_parcel.  PySDM's default formulae go to
-    the default kernel unless `general` (the two must agree bit for bit)"""
+    the default kernel unless `general` (the two must agree bit for bit).  With `requests` (an
+    abi.ParcelRequests) the call is `sdm_parcel_run_diag`, and `diag` a dict of engine arrays by
+    the member names of sdm_parcel_diag (members may be missing)"""
     if descriptor is None:
         descriptor = check_formulae(formulae)
     n_parcel = engine.size(parcel_start) - 1
@@ -101,11 +107,49 @@ def parcel_call(engine, formulae, cfg, *, n_steps, parcel_start, water_mass, mul
             setattr(c_profile, name,
                     _address(array, INT if name.startswith("n_") else FLOAT))
     consts = [float(getattr(formulae.constants, name)) for name in CONSTANT_NAMES]
-    engine.call_parcel(
-        "sdm_parcel_run", cfg, int(n_steps), int(n_parcel), int(engine.size(water_mass)),
-        parcel_start, water_mass, multiplicity, dry_volume, kappa, f_org, critical_volume,
-        c_state, w_mid, c_profile, consts,
-        None if is_default(descriptor) and not general else descriptor)
+    args = (cfg, int(n_steps), int(n_parcel), int(engine.size(water_mass)),
+            parcel_start, water_mass, multiplicity, dry_volume, kappa, f_org, critical_volume,
+            c_state, w_mid, c_profile, consts,
+            None if is_default(descriptor) and not general else descriptor)
+    if requests is None:
+        engine.call_parcel("sdm_parcel_run", *args)
+        return
+    sizes = {"moment_0": requests.n_moments, "moments": requests.n_moments,
+             "spectrum": requests.n_bins, "dv": 1}
+    engine.call_parcel_diag("sdm_parcel_run_diag", *args, requests,
+                            _diag_struct(engine, diag, sizes, n_steps * n_parcel))
+
+
+def _diag_struct(engine, diag, sizes, n_rows):
+    """abi.ParcelDiag of a dict of engine arrays (None: no outputs)"""
+    if diag is None:
+        return None
+    c_diag = abi.ParcelDiag()
+    for name in abi.PARCEL_DIAG_FIELDS:
+        array = diag.get(name)
+        if array is not None and engine.size(array) != n_rows * sizes[name]:
+            raise ValueError(f"parcel: diag[{name!r}] must hold {n_rows} x {sizes[name]} values")
+        setattr(c_diag, name, _address(array, FLOAT))
+    return c_diag
+
+
+def diagnose_call(engine, formulae, requests, *, parcel_start, water_mass, multiplicity,
+                  dry_volume, kappa, f_org, T, diag, descriptor=None, general=False):
+    """one `sdm_parcel_diagnose` call with raw engine arrays: the request table on given columns
+    at one temperature per parcel; `diag` as in `parcel_call` (without dv)"""
+    if descriptor is None:
+        descriptor = check_formulae(formulae)
+    n_parcel = engine.size(parcel_start) - 1
+    if engine.size(T) != n_parcel:
+        raise ValueError("parcel: T must hold n_parcel values")
+    sizes = {"moment_0": requests.n_moments, "moments": requests.n_moments,
+             "spectrum": requests.n_bins, "dv": 0}
+    consts = [float(getattr(formulae.constants, name)) for name in CONSTANT_NAMES]
+    engine.call_parcel_diag(
+        "sdm_parcel_diagnose", int(n_parcel), int(engine.size(water_mass)), parcel_start,
+        water_mass, multiplicity, dry_volume, kappa, f_org, T, consts,
+        None if is_default(descriptor) and not general else descriptor, requests,
+        _diag_struct(engine, {k: v for k, v in diag.items() if k != "dv"}, sizes, n_parcel))
 
 
 class ParcelRunner:  # pylint: disable=too-many-instance-attributes
@@ -196,6 +240,9 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
         self.critical_volume = engine.full(n_sd, FLOAT, np.nan)
         self.n_steps = 0  # time steps asked for so far: the clock of w(t)
         self.last_profile = None
+        self.last_products = None
+        self.last_rows = None
+        self.diag_fill = np.nan  # what the rows of steps a failed parcel did not carry out hold
         self._reported = set()
 
     # ---- construction from a spectrum ---------------------------------------------------------
@@ -261,10 +308,63 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
         return out
 
     # ---- running ----------------------------------------------------------------------------------
-    def run(self, n_steps, profile=True):
+    def _table(self, products):
+        if self.engine.parcel_diag_library is None:
+            raise NotImplementedError(f"engine `{self.engine.name}` has no parcel-diagnostics "
+                                      "library: products are not available on it")
+        return products if isinstance(products, RequestTable) else RequestTable(products,
+                                                                                self.formulae)
+
+    def _diag_arrays(self, table, n_rows, dv=True):
+        """engine arrays for `n_rows` rows of the table's outputs, prefilled with `diag_fill`
+        (NaN): rows of steps a failed parcel did not carry out stay so"""
+        eng = self.engine
+        sizes = {"moment_0": table.n_moments, "moments": table.n_moments,
+                 "spectrum": table.n_bins, "dv": 1 if dv else 0}
+        return {name: eng.full(n_rows * size, FLOAT, self.diag_fill) for name, size in sizes.items()
+                if size > 0}
+
+    def _rows(self, table, diag, shape, rhod, dv=None):
+        down = self.engine.download
+
+        def get(name, width):
+            if name not in diag:  # (no such requests, or no steps)
+                return np.full((*shape, width), np.nan)
+            return down(diag[name]).reshape(*shape, width)
+
+        return Rows(table, moment_0=get("moment_0", table.n_moments),
+                    moments=get("moments", table.n_moments),
+                    spectrum=get("spectrum", table.n_bins),
+                    dv=down(diag["dv"]).reshape(shape) if dv is None else dv, rhod=rhod)
+
+    def diagnose(self, products, dv=None):
+        """the products of the current state, {name: array of n_parcel (x n_bins)}: the request
+        table on the runner's columns at the parcels' temperatures (`sdm_parcel_diagnose`).  `dv`
+        defaults to mass_of_dry_air / rhod, `mesh.dv` of a parcel that has not moved yet (after a
+        step PySDM's mesh.dv is the step's mid-point volume, which `run` reports)"""
+        table = self._table(products)
+        diag = self._diag_arrays(table, self.n_parcel, dv=False)
+        diagnose_call(self.engine, self.formulae, table.c_struct(),
+                      parcel_start=self.parcel_start, water_mass=self.water_mass,
+                      multiplicity=self.multiplicity, dry_volume=self.dry_volume,
+                      kappa=self.kappa, f_org=self.f_org, T=self.state["T"], diag=diag,
+                      descriptor=self.descriptor, general=self.general)
+        rhod = self.engine.download(self.state["rhod"])
+        if dv is None:
+            dv = self.engine.download(self.state["mass_of_dry_air"]) / rhod
+        rows = self._rows(table, diag, (self.n_parcel,), rhod,
+                          dv=np.broadcast_to(np.asarray(dv, dtype=float), (self.n_parcel,)))
+        self.last_rows = rows
+        return table.values(rows)
+
+    def run(self, n_steps, profile=True, products=()):
         """`n_steps` further time steps of every parcel that has not failed; returns the profile
         (host arrays of n_steps x n_parcel by the names of sdm_parcel_profile; entries of steps a
-        failed parcel did not carry out are NaN / -1) or None.  Raises
+        failed parcel did not carry out are NaN / -1) or None.  With `products` (a sequence of
+        pysdm_amd.products objects, or a RequestTable) it returns (profile, {product name: array
+        of n_steps x n_parcel (x n_bins)}): the products of the state after every step (NaN for
+        steps a failed parcel did not carry out); the evaluated table itself is kept in
+        `last_rows`.  Raises
         RuntimeError("Condensation failed", parcel, step) after the call for the first parcel whose
         solver failed in it: the other parcels' state stays valid (and the profile is kept in
         `last_profile`); a failed parcel is skipped from then on"""
@@ -273,8 +373,15 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
             raise ValueError("n_steps must not be negative")
         eng, n_parcel = self.engine, self.n_parcel
         record = None
+        table = self._table(products) if isinstance(products, RequestTable) or len(products) \
+            else None
+        diag = None
         if n_steps > 0:
             w_mid = self.w_mid(n_steps)
+            if table is not None:
+                diag = self._diag_arrays(table, n_steps * n_parcel)
+                if not profile:  # (the specific products divide by the step's rhod)
+                    record = {"rhod": eng.full(n_steps * n_parcel, FLOAT, np.nan)}
             if profile:
                 record = {name: eng.full(n_steps * n_parcel, INT, -1) if name.startswith("n_")
                           else eng.full(n_steps * n_parcel, FLOAT, np.nan)
@@ -286,21 +393,30 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
                             kappa=self.kappa, f_org=self.f_org,
                             critical_volume=self.critical_volume, state=self.state,
                             w_mid=eng.upload(w_mid.reshape(-1)), profile=record,
-                            descriptor=self.descriptor, general=self.general)
+                            descriptor=self.descriptor, general=self.general,
+                            requests=None if table is None else table.c_struct(), diag=diag)
             else:
-                self._run_stages(w_mid, record)
+                self._run_stages(w_mid, record, table, diag)
             self.n_steps += n_steps
         out = None
         if record is not None:
             out = {name: eng.download(array).reshape(n_steps, n_parcel)
                    for name, array in record.items()}
-        self.last_profile = out
+        values = None
+        if table is not None:
+            shape = (n_steps, n_parcel)
+            rhod = out["rhod"] if n_steps > 0 else np.empty(shape)
+            self.last_rows = self._rows(table, diag or {"dv": eng.empty(0, FLOAT)}, shape, rhod)
+            values = table.values(self.last_rows)
+            if not profile:
+                out = None
+        self.last_profile, self.last_products = out, values
         failed = eng.download(self.state["failed_step"])
         for parcel in np.flatnonzero(failed >= 0):
             if int(parcel) not in self._reported:
                 self._reported.update(int(p) for p in np.flatnonzero(failed >= 0))
                 raise RuntimeError("Condensation failed", int(parcel), int(failed[parcel]))
-        return out
+        return out if table is None else (out, values)
 
     def _latent_heat(self, T, scratch):
         """formulae.latent_heat_vapourisation.lv(T) in the library's arithmetic: Kirchhoff and
@@ -318,9 +434,16 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
             return const.l_tri * float(eng.download(scratch)[0])
         return const.l_tri + (const.c_pv - const.c_pw) * (T - const.T_tri)
 
-    def _run_stages(self, w_mid, record):  # pylint: disable=too-many-locals,too-many-statements
-        """the time step of include/sdm_parcel.h with the stage symbols, parcel after parcel"""
+    def _run_stages(self, w_mid, record, table=None, diag=None):  # pylint: disable=too-many-locals,too-many-statements
+        """the time step of include/sdm_parcel.h with the stage symbols, parcel after parcel; the
+        products' table with `sdm_parcel_diagnose` on the parcel's slice after each step"""
         eng, const, cfg, setup = self.engine, self.formulae.constants, self.cfg, self.setup
+        diag_rows = {name: eng.download(array) for name, array in (diag or {}).items()}
+        if table is not None:
+            requests = table.c_struct()
+            one_diag = self._diag_arrays(table, 1, dv=False)
+            widths = {"moment_0": table.n_moments, "moments": table.n_moments,
+                      "spectrum": table.n_bins}
         host = {name: eng.download(array) for name, array in self.state.items()}
         rows = {name: (eng.download(array) if array is not None else None)
                 for name, array in (record or {}).items()}
@@ -404,6 +527,19 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
                 for name, row in rows.items():
                     if row is not None:
                         row[k * n_parcel + c] = host[name][c]
+                if table is not None:
+                    at = k * n_parcel + c
+                    diagnose_call(eng, self.formulae, requests, parcel_start=cell_start,
+                                  water_mass=mass, multiplicity=self.multiplicity[r0:r1],
+                                  dry_volume=self.dry_volume[r0:r1], kappa=self.kappa[r0:r1],
+                                  f_org=self.f_org[r0:r1], T=one["T"], diag=one_diag,
+                                  descriptor=self.descriptor, general=self.general)
+                    diag_rows["dv"][at] = dv
+                    for name, array in one_diag.items():
+                        width = widths[name]
+                        diag_rows[name][at * width:(at + 1) * width] = eng.download(array)
+        for name, row in diag_rows.items():
+            eng.assign(diag[name], eng.upload(row))
         for name, array in self.state.items():
             eng.assign(array, eng.upload(host[name]))
         for name, row in rows.items():

@@ -506,7 +506,7 @@ _PARCEL_VARS = {"z": "z", "rhod": "rhod", "thd": "thd", "qv": "water_vapour_mixi
                 "T": "T", "p": "p", "RH": "RH"}
 
 
-def run_parcel(particulator, steps):
+def run_parcel(particulator, steps, products=()):
     """`steps` time steps of a built `Particulator` whose environment is a `Parcel` and whose
     dynamics are exactly `AmbientThermodynamics` and `Condensation`, in ONE `sdm_parcel_run` on the
     particulator's own arrays (include/sdm_parcel.h; anything else: ValueError).  It leaves the
@@ -514,9 +514,11 @@ def run_parcel(particulator, steps):
     environment's current values and the previous ones that `sync_parcel_vars` reads next, the
     dynamic's counters, `rh_max` and `success`, and `n_steps`.
 
-    Observers and products are NOT notified per step: there is no per-step hook inside the kernel.
-    Read products before and after, or keep `particulator.run` where every step must be seen.
-    Returns the profile (host arrays of `steps` values by the names of sdm_parcel_profile)"""
+    Observers and PySDM's own product objects are NOT notified per step.  `products` (objects of
+    pysdm_amd.products, which carry PySDM's names, arguments and units) are evaluated inside the
+    kernel's step loop after every step (`sdm_parcel_run_diag`, include/sdm_parcel_diag.h).
+    Returns the profile (host arrays of `steps` values by the names of sdm_parcel_profile), or with
+    `products` {product name: array of `steps` values (x bins)}"""
     from . import parcel as _parcel  # pylint: disable=import-outside-toplevel
     from .condensation import CondensationSetup, check_formulae  # pylint: disable=import-outside-toplevel
     from .engine import FLOAT, INT  # pylint: disable=import-outside-toplevel
@@ -575,6 +577,16 @@ def run_parcel(particulator, steps):
         raise ValueError("run_parcel: the updraft must be finite and non-zero at every step's "
                          "mid-point")
     record = {name: eng.full(steps, FLOAT, np.nan) for name in _PARCEL_VARS}
+    table = diag = None
+    if len(products):
+        from .products import RequestTable  # pylint: disable=import-outside-toplevel
+
+        if eng.parcel_diag_library is None:
+            raise NotImplementedError(f"engine `{eng.name}` has no parcel-diagnostics library")
+        table = RequestTable(products, formulae)
+        diag = {name: eng.full(steps * size, FLOAT, np.nan) for name, size in
+                (("moment_0", table.n_moments), ("moments", table.n_moments),
+                 ("spectrum", table.n_bins), ("dv", 1)) if size > 0}
     _parcel.parcel_call(
         eng, formulae, cfg, n_steps=steps,
         parcel_start=eng.upload(np.array([0, n_sd], dtype=np.int64)),
@@ -582,7 +594,8 @@ def run_parcel(particulator, steps):
         dry_volume=attrs["dry volume"].data, kappa=attrs["kappa"].data,
         f_org=attrs["dry volume organic fraction"].data,
         critical_volume=eng.empty(n_sd, FLOAT), state=state, w_mid=eng.upload(w_mid),
-        profile=record, descriptor=descriptor)
+        profile=record, descriptor=descriptor,
+        requests=None if table is None else table.c_struct(), diag=diag)
     attrs.mark_updated("signed water mass")
     done = int(eng.download(state["steps_done"])[0])
     rows = {name: eng.download(array) for name, array in record.items()}
@@ -603,4 +616,15 @@ def run_parcel(particulator, steps):
     if done < steps:
         eng.fill(dynamic.success.data, False)
         raise RuntimeError("Condensation failed")
-    return rows
+    if table is None:
+        return rows
+    from .products import Rows  # pylint: disable=import-outside-toplevel
+
+    def column(name, width):
+        return eng.download(diag[name]).reshape(steps, width) if name in diag \
+            else np.empty((steps, 0))
+
+    return table.values(Rows(table, moment_0=column("moment_0", table.n_moments),
+                             moments=column("moments", table.n_moments),
+                             spectrum=column("spectrum", table.n_bins),
+                             dv=eng.download(diag["dv"]), rhod=rows["rhod"]))

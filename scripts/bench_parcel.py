@@ -14,6 +14,16 @@ same restored state, a warm-up call first; the figure is the median of --reps ca
 single launch is measured separately: the same ascent as calls of `steps_per_launch` steps, each
 one launch, the slowest of them reported.  Writes profiles/parcel_timing.json and prints it; a
 measurement, not a test: no threshold, no ratio fixed in advance.
+
+`--products` is a measurement of its own (the output above does not change): 1, 16 and 256
+parcels, the fused route with `products=()` and with the eleven products of pysdm_amd/products.py
+and a 64-bin spectrum (`sdm_parcel_run_diag`: the request table evaluated inside the kernel's step
+loop; the rows' download is part of the timed call), and at 1 and 16 parcels the route that
+existed before: `run(1)`, `snapshot()` and `diagnostics.moments` / `spectrum_moments` on a
+`Population` of the snapshot, per step (it has no activation filter: it computes the moments of
+the five unfiltered products and the spectrum only).  `--products-stepwise-only` times just the
+latter, which needs nothing of this module's newer interfaces.  Writes
+profiles/parcel_products_timing.json.
 """
 import argparse
 import json
@@ -45,7 +55,7 @@ def make_runner(kind, n_parcel, route, steps_per_launch, engine=None):
         route=route, steps_per_launch=steps_per_launch)
 
 
-def timed(runner, start, steps, reps, warmup):
+def timed(runner, start, steps, reps, warmup, call=None):
     import torch  # pylint: disable=import-outside-toplevel
 
     samples = []
@@ -54,7 +64,10 @@ def timed(runner, start, steps, reps, warmup):
         begin, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         torch.cuda.synchronize()
         begin.record()
-        runner.run(steps, profile=False)
+        if call is None:
+            runner.run(steps, profile=False)
+        else:
+            call(runner, steps)
         end.record()
         end.synchronize()
         if rep >= warmup:
@@ -89,6 +102,84 @@ def measure(kind, n_parcel, route, reps, warmup, steps_per_launch):
 
 
 SPL_DEFAULT = 16  # SDM_PARCEL_STEPS_PER_LAUNCH of include/sdm_parcel.h
+PRODUCT_SIZES = (1, 16, 256)
+SPECTRUM_EDGES = np.geomspace(2e-8, 2e-5, 65)
+
+
+def eleven_products():
+    from pysdm_amd import products as pr  # pylint: disable=import-outside-toplevel
+
+    act = dict(count_unactivated=False, count_activated=True)
+    return (pr.ParticleConcentration(), pr.ParticleSpecificConcentration(),
+            pr.WaterMixingRatio(), pr.MeanRadius(), pr.EffectiveRadius(),
+            pr.ActivatedParticleConcentration(**act),
+            pr.ActivatedParticleSpecificConcentration(**act), pr.ActivatedMeanRadius(**act),
+            pr.ActivatedEffectiveRadius(**act),
+            pr.ParticleSizeSpectrumPerMassOfDryAir(radius_bins_edges=SPECTRUM_EDGES),
+            pr.ParticleSizeSpectrumPerVolume(radius_bins_edges=SPECTRUM_EDGES))
+
+
+def stepwise(runner, steps):
+    """the products' moments the way they could be had before: per step one `run(1)`, a
+    `snapshot()` and `diagnostics.moments` / `spectrum_moments` on a Population of it"""
+    from pysdm_amd import diagnostics  # pylint: disable=import-outside-toplevel
+    from pysdm_amd.population import Population  # pylint: disable=import-outside-toplevel
+
+    eng = runner.engine
+    multiplicity = eng.download(runner.multiplicity)
+    cell_id = np.repeat(np.arange(runner.n_parcel), np.diff(runner.parcel_start_host))
+    volume_edges = 4 / 3 * np.pi * SPECTRUM_EDGES ** 3
+    out = []
+    for _ in range(steps):
+        profile = runner.run(1)
+        state = runner.snapshot()
+        population = Population(eng, multiplicity=multiplicity, mass=state["water_mass"],
+                                cell_id=cell_id, n_cell=runner.n_parcel)
+        out.append((
+            profile["rhod"],
+            diagnostics.moments(population, [0, 1], attr="water mass"),  # (host arrays)
+            diagnostics.moments(population, [1 / 3, 2 / 3, 1]),
+            diagnostics.spectrum_moments(population, volume_edges, bin_attr="volume")))
+    return out
+
+
+def measure_products(kind, n_parcel, mode, reps, warmup):
+    runner = make_runner(kind, n_parcel, "fused", 0)
+    start = runner.snapshot()
+    if mode == "stepwise":
+        call = stepwise
+    elif mode == "fused":
+        call = None
+    else:
+        products = eleven_products()
+        call = lambda r, steps: r.run(steps, profile=False, products=products)  # noqa: E731
+    samples = timed(runner, start, STEPS, reps, warmup, call)
+    final = runner.snapshot()
+    assert (final["failed_step"] == -1).all() and (final["steps_done"] == STEPS).all()
+    ms = float(np.median(samples))
+    return {"formulae": kind, "mode": mode, "n_parcel": n_parcel, "n_sd_per_parcel": N_SD,
+            "steps": STEPS, "reps": reps, "ms_median": round(ms, 3),
+            "ms_min": round(float(np.min(samples)), 3),
+            "ms_max": round(float(np.max(samples)), 3),
+            "ms_per_parcel_step": round(ms / (n_parcel * STEPS), 5)}
+
+
+def main_products(args):
+    results = []
+    for kind in ("default", "lowe2019"):
+        modes = [] if args.products_stepwise_only else [
+            (mode, n) for n in PRODUCT_SIZES for mode in ("fused", "fused+products")]
+        modes += [("stepwise", n) for n in STAGE_SIZES]
+        for mode, n_parcel in modes:
+            results.append(measure_products(kind, n_parcel, mode, args.reps, args.warmup))
+            print(json.dumps(results[-1]), flush=True)
+    out = args.out or os.path.join(ROOT, "profiles", "parcel_products_timing.json")
+    with open(out, "w", encoding="utf-8") as handle:
+        handle.write(json.dumps({
+            "workload": f"{N_SD} super-droplets per parcel, {STEPS} steps of {DT} s, updrafts "
+                        "0.2 .. 5 m/s (2 m/s for one parcel); eleven products, 64 bins",
+            "results": results}, indent=1) + "\n")
+    print("wrote", out)
 
 
 def main():
@@ -96,8 +187,17 @@ def main():
     parser.add_argument("--reps", type=int, default=5)
     parser.add_argument("--warmup", type=int, default=1)
     parser.add_argument("--steps-per-launch", type=int, default=0, help="0: the library's default")
-    parser.add_argument("--out", default=os.path.join(ROOT, "profiles", "parcel_timing.json"))
+    parser.add_argument("--out", default=None,
+                        help="default: profiles/parcel_timing.json (parcel_products_timing.json "
+                             "with --products)")
+    parser.add_argument("--products", action="store_true",
+                        help="time the products instead (see the module's docstring)")
+    parser.add_argument("--products-stepwise-only", action="store_true")
     args = parser.parse_args()
+    if args.products or args.products_stepwise_only:
+        main_products(args)
+        return
+    args.out = args.out or os.path.join(ROOT, "profiles", "parcel_timing.json")
     results = []
     for kind in ("default", "lowe2019"):
         for n_parcel in SIZES:
