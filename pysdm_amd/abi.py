@@ -43,6 +43,8 @@ INITIALISATION_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include",
 PARCEL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "sdm_parcel.h")
 # and the parcel's diagnostics (moments and a size spectrum per step)
 PARCEL_DIAG_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "sdm_parcel_diag.h")
+# and the parcel with aqueous chemistry (cloud processing of aerosol)
+PARCEL_CHEM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "sdm_parcel_chem.h")
 # SDM_HIP_LIB: another build of the same library (tuning variants); still no fallback
 HIP_LIB_PATH = os.environ.get("SDM_HIP_LIB") or os.path.join(_HERE, "libsdm_hip.so")
 
@@ -215,6 +217,11 @@ class ParcelRequests(ctypes.Structure):  # == sdm_parcel_requests
 
 class ParcelDiag(ctypes.Structure):  # == sdm_parcel_diag
     _fields_ = [(name, c_ptr) for name in PARCEL_DIAG_FIELDS]
+
+
+class ParcelChemProfile(ctypes.Structure):  # == sdm_parcel_chem_profile (include/sdm_parcel_chem.h)
+    _fields_ = [("mixing_ratio", c_ptr * 6), ("aq_total", c_ptr * 7), ("n_flagged", c_ptr),
+                ("dv", c_ptr)]
 
 
 class RelaxedVelocityCfg(ctypes.Structure):  # == sdm_relaxed_velocity_cfg
@@ -394,6 +401,7 @@ _relaxed_velocity_library = None
 _initialisation_library = None
 _parcel_library = None
 _parcel_diag_library = None
+_parcel_chem_library = None
 
 
 def hip_library():
@@ -492,6 +500,15 @@ def parcel_diag_library():
         _parcel_diag_library = Library(HIP_LIB_PATH, "the HIP kernels of pysdm_amd",
                                        header=PARCEL_DIAG_HEADER_PATH)
     return _parcel_diag_library
+
+
+def parcel_chem_library():
+    """libsdm_hip.so bound to include/sdm_parcel_chem.h (same file, same contexts)"""
+    global _parcel_chem_library  # pylint: disable=global-statement
+    if _parcel_chem_library is None:
+        _parcel_chem_library = Library(HIP_LIB_PATH, "the HIP kernels of pysdm_amd",
+                                       header=PARCEL_CHEM_HEADER_PATH)
+    return _parcel_chem_library
 
 
 def pcg64_state_inc(seed):

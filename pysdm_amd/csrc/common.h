@@ -122,6 +122,10 @@ struct sdm_ctx {
   // the request table of the current sdm_parcel_run_diag / sdm_parcel_diagnose call in device
   // memory (one sdm_parcel_requests, allocated at the first such call)
   void *parcel_requests;
+  // parcel_chem.hip: rhod before the step per parcel, and the staged multiplicity * (new - old) and
+  // `took` marks of parcels too large for registers (one buffer, grown on demand)
+  char *parcel_chem_buf;
+  size_t parcel_chem_bytes;
   // device control words for fine-grained calls (int64[16]; word 6: dt_left[0] of an adaptive
   // single cell for the next sub-step, fused.hip; 8: a length; 10-11: adaptive_end; 12-15: barrier)
   int64_t *dscal;

@@ -129,6 +129,7 @@ extern "C" int sdm_ctx_destroy(sdm_ctx *ctx) {
   if (ctx->parcel_identity) (void)hipFree(ctx->parcel_identity);
   if (ctx->parcel_backup) (void)hipFree(ctx->parcel_backup);
   if (ctx->parcel_requests) (void)hipFree(ctx->parcel_requests);
+  if (ctx->parcel_chem_buf) (void)hipFree(ctx->parcel_chem_buf);
   if (ctx->graph_exec) (void)hipGraphExecDestroy((hipGraphExec_t)ctx->graph_exec);
   free(ctx->graph_key);
   if (ctx->gwords) (void)hipFree(ctx->gwords);

@@ -95,15 +95,16 @@ extern "C" int sdm_parcel_run(sdm_ctx *ctx, const sdm_parcel_cfg *cfg, int64_t n
                              formulae, nullptr, nullptr);
 }
 
-extern "C" int sdm_parcel_run_diag(sdm_ctx *ctx, const sdm_parcel_cfg *cfg, int64_t n_steps,
-                                   int64_t n_parcel, int64_t n_sd, const int64_t *parcel_start,
-                                   double *water_mass, const int64_t *multiplicity,
-                                   const double *vdry, const double *kappa, const double *f_org,
-                                   double *v_cr, const sdm_parcel_state *state,
-                                   const double *w_mid, const sdm_parcel_profile *profile,
-                                   const double consts[34], const sdm_cond_formulae *formulae,
-                                   const sdm_parcel_requests *requests,
-                                   const sdm_parcel_diag *diag) {
+int sdm_parcel_prepare(sdm_ctx *ctx, const sdm_parcel_cfg *cfg, int64_t n_steps, int64_t n_parcel,
+                       int64_t n_sd, const int64_t *parcel_start, double *water_mass,
+                       const int64_t *multiplicity, const double *vdry, const double *kappa,
+                       const double *f_org, double *v_cr, const sdm_parcel_state *state,
+                       const double *w_mid, const sdm_parcel_profile *profile,
+                       const double consts[34], const sdm_cond_formulae *formulae,
+                       const sdm_parcel_requests *requests, const sdm_parcel_diag *diag,
+                       ParcelCall *out, bool *with_diag_out, bool *nothing_to_do) {
+  *nothing_to_do = true;
+  *with_diag_out = false;
   ARG_TRY(ctx && cfg && consts && state);
   ARG_TRY(n_steps >= 0 && n_parcel >= 0 && n_sd >= 0 && n_parcel <= 0x7fffffff);
   ARG_TRY(cfg->multiplier >= 1 && cfg->fuse >= 0 && cfg->max_iters >= 0 && cfg->dt > 0);
@@ -132,7 +133,7 @@ extern "C" int sdm_parcel_run_diag(sdm_ctx *ctx, const sdm_parcel_cfg *cfg, int6
   const int rc = reserve_rows(ctx, n_sd);
   if (rc != SDM_OK) return rc;
 
-  ParcelCall call;
+  ParcelCall &call = *out;
   call.cfg = *cfg;
   call.n_parcel = n_parcel;
   call.n_sd = n_sd;
@@ -153,6 +154,28 @@ extern "C" int sdm_parcel_run_diag(sdm_ctx *ctx, const sdm_parcel_cfg *cfg, int6
   call.requests = with_diag ? (const sdm_parcel_requests *)ctx->parcel_requests : nullptr;
   if (with_diag) call.diag = *diag;
   else memset(&call.diag, 0, sizeof(call.diag));
+  call.k0 = call.k_count = 0;
+  *with_diag_out = with_diag;
+  *nothing_to_do = false;
+  return SDM_OK;
+}
+
+extern "C" int sdm_parcel_run_diag(sdm_ctx *ctx, const sdm_parcel_cfg *cfg, int64_t n_steps,
+                                   int64_t n_parcel, int64_t n_sd, const int64_t *parcel_start,
+                                   double *water_mass, const int64_t *multiplicity,
+                                   const double *vdry, const double *kappa, const double *f_org,
+                                   double *v_cr, const sdm_parcel_state *state,
+                                   const double *w_mid, const sdm_parcel_profile *profile,
+                                   const double consts[34], const sdm_cond_formulae *formulae,
+                                   const sdm_parcel_requests *requests,
+                                   const sdm_parcel_diag *diag) {
+  ParcelCall call;
+  bool with_diag, nothing_to_do;
+  const int prepared = sdm_parcel_prepare(ctx, cfg, n_steps, n_parcel, n_sd, parcel_start,
+                                          water_mass, multiplicity, vdry, kappa, f_org, v_cr, state,
+                                          w_mid, profile, consts, formulae, requests, diag, &call,
+                                          &with_diag, &nothing_to_do);
+  if (prepared != SDM_OK || nothing_to_do) return prepared;
   const int64_t per_launch =
       cfg->steps_per_launch > 0 ? cfg->steps_per_launch : SDM_PARCEL_STEPS_PER_LAUNCH;
   for (int64_t k0 = 0; k0 < n_steps; k0 += per_launch) {
@@ -196,6 +219,7 @@ extern "C" int sdm_parcel_diagnose(sdm_ctx *ctx, int64_t n_parcel, int64_t n_sd,
   call.requests = (const sdm_parcel_requests *)ctx->parcel_requests;
   call.diag = *diag;
   call.diag.dv = nullptr;
+  call.failed_step = nullptr;
   return formulae ? sdm_parcel_diagnose_general(ctx, call, formulae)
                   : sdm_parcel_diagnose_default(ctx, call);
 }

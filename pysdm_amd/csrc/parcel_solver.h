@@ -67,7 +67,21 @@ struct ParcelDiagnoseCall {
   const double *water_mass, *vdry, *kappa, *f_org, *T, *consts;
   const sdm_parcel_requests *requests;
   sdm_parcel_diag diag;
+  // sdm_parcel_run_chem: parcels with failed_step[c] >= 0 are skipped (nullptr: none is)
+  const int64_t *failed_step = nullptr;
 };
+// parcel.hip: the checks of sdm_parcel_run_diag and the ParcelCall of its arguments (k0 / k_count
+// left to the caller); *with_diag: the request table is in device memory and `diag` has outputs.
+// It synchronises the stream once (parcel_start is read back).  n_parcel or n_steps 0: SDM_OK with
+// *nothing_to_do set
+int sdm_parcel_prepare(sdm_ctx *ctx, const sdm_parcel_cfg *cfg, int64_t n_steps, int64_t n_parcel,
+                       int64_t n_sd, const int64_t *parcel_start, double *water_mass,
+                       const int64_t *multiplicity, const double *vdry, const double *kappa,
+                       const double *f_org, double *v_cr, const sdm_parcel_state *state,
+                       const double *w_mid, const sdm_parcel_profile *profile,
+                       const double consts[34], const sdm_cond_formulae *formulae,
+                       const sdm_parcel_requests *requests, const sdm_parcel_diag *diag,
+                       ParcelCall *call, bool *with_diag, bool *nothing_to_do);
 // condensation.hip / condensation_formulae.hip: one launch of the default / general kernel
 int sdm_parcel_launch_default(sdm_ctx *ctx, const ParcelCall &call);
 int sdm_parcel_launch_general(sdm_ctx *ctx, const ParcelCall &call,
@@ -105,6 +119,7 @@ struct ParcelDiagnoseArgs {
   const int64_t *parcel_start, *multiplicity;
   const double *water_mass, *vdry, *kappa, *T;
   ParcelDiag d;
+  const int64_t *failed_step;
 };
 
 #define DIAG_ROUND 4  // sums reduced at a time: moment_0 and moments of two requests
@@ -239,6 +254,7 @@ DF void parcel_diagnose_cells(const ParcelDiagnoseArgs<P> &a) {
   for (int64_t c = blockIdx.x; c < a.n_parcel; c += gridDim.x) {
     const int64_t row0 = a.parcel_start[c], n = a.parcel_start[c + 1] - row0;
     if (row0 < 0 || n <= 0 || row0 + n > a.n_sd) continue;  // (checked on the host too)
+    if (a.failed_step && a.failed_step[c] >= 0) continue;   // (uniform over the workgroup)
     parcel_diagnose<P>(a.k, a.d.req, l, row0, n, a.T[c], a.water_mass, a.multiplicity, a.vdry,
                        a.kappa, a.d.out.moment_0 ? a.d.out.moment_0 + c * nm : nullptr,
                        a.d.out.moments ? a.d.out.moments + c * nm : nullptr,
@@ -448,6 +464,7 @@ DF void parcel_steps(const ParcelArgs<P> &a, const ParcelDiag *d = nullptr) {
     (a).T = (call).T;                          \
     (a).d.req = (call).requests;               \
     (a).d.out = (call).diag;                   \
+    (a).failed_step = (call).failed_step;      \
   } while (0)
 #endif  // __HIPCC__
 

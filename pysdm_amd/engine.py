@@ -41,6 +41,8 @@ class Engine:
     parcel_library = None
     # likewise include/sdm_parcel_diag.h
     parcel_diag_library = None
+    # likewise include/sdm_parcel_chem.h
+    parcel_chem_library = None
     # whether the fused collision step of `library` can take the fall velocity from the
     # "relative fall momentum" row; an engine that cannot must refuse, not ignore the request
     fused_momentum_velocity = False
@@ -158,6 +160,14 @@ class Engine:
         self._before_call()
         self.parcel_diag_library.invoke(symbol, self.handle, args)
 
+    def call_parcel_chem(self, symbol, *args):
+        """a symbol of include/sdm_parcel_chem.h"""
+        if self.parcel_chem_library is None:
+            raise NotImplementedError(
+                f"engine `{self.name}` has no library for the parcel with aqueous chemistry")
+        self._before_call()
+        self.parcel_chem_library.invoke(symbol, self.handle, args)
+
     def _before_call(self):
         pass
 
@@ -196,6 +206,7 @@ class HipEngine(Engine):
         self.initialisation_library = abi.initialisation_library()
         self.parcel_library = abi.parcel_library()
         self.parcel_diag_library = abi.parcel_diag_library()
+        self.parcel_chem_library = abi.parcel_chem_library()
         self.handle = abi.c_ptr()
         self.library.check(self.library.cdll.sdm_ctx_create(ctypes.byref(self.handle),
                                                             abi.c_int(device_index)))

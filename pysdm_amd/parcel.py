@@ -24,6 +24,7 @@ kernel's step loop (`sdm_parcel_run_diag`, include/sdm_parcel_diag.h), the stage
 import numpy as np
 
 from . import abi
+from . import chemistry as chem
 from .condensation import (CONSTANT_NAMES, OPTION_ORDER, _option_name, check_formulae,
                            condensation_call, critical_volume_call, is_default,
                            temperature_pressure_rh_call)
@@ -36,6 +37,9 @@ ROUTES = ("fused", "stages")
 _INT_FIELDS = ("n_substeps", "n_activating", "n_deactivating", "n_ripening", "steps_done",
                "failed_step")
 _LV = OPTION_ORDER.index("latent_heat_vapourisation")
+_SGM = OPTION_ORDER.index("surface_tension")
+CHEM_COUNTERS = ("n_failed", "n_negative", "n_exceeded")
+_DIAG_LANES = 256  # the partials of the SUM of include/sdm_parcel_diag.h
 
 
 def _address(array, dtype):
@@ -80,13 +84,18 @@ def parcel_cfg(formulae, setup, dt, steps_per_launch=0):
 
 def parcel_call(engine, formulae, cfg, *, n_steps, parcel_start, water_mass, multiplicity,
                 dry_volume, kappa, f_org, critical_volume, state, w_mid, profile=None,
-                descriptor=None, general=False, requests=None, diag=None):
+                descriptor=None, general=False, requests=None, diag=None, chem=None):
     """one `sdm_parcel_run` call with raw engine arrays: `state` / `profile` are dicts of engine
     arrays by the member names of sdm_parcel_state / sdm_parcel_profile (`profile` may be None or
     lack members), `w_mid` an engine array of n_steps x n_parcel.  PySDM's default formulae go to
     the default kernel unless `general` (the two must agree bit for bit).  With `requests` (an
     abi.ParcelRequests) the call is `sdm_parcel_run_diag`, and `diag` a dict of engine arrays by
-    the member names of sdm_parcel_diag (members may be missing)"""
+    the member names of sdm_parcel_diag (members may be missing).  With `chem` the call is
+    `sdm_parcel_run_chem` (include/sdm_parcel_chem.h): a dict with `cfg` (abi.ChemistryCfg),
+    `kappa_times_dry_volume`, `moles` (7 columns), `pH`, `do_chemistry_flag`, `mixing_ratios` (6
+    arrays of n_parcel), `consts` (62), `dry_factor`, `counters` (3 arrays of n_parcel or None)
+    and `profile` (None, or a dict with `mixing_ratio`: 6 arrays, `aq_total`: 7 arrays,
+    `n_flagged`, `dv`, each of n_steps x n_parcel; entries may be missing)"""
     if descriptor is None:
         descriptor = check_formulae(formulae)
     n_parcel = engine.size(parcel_start) - 1
@@ -111,13 +120,58 @@ def parcel_call(engine, formulae, cfg, *, n_steps, parcel_start, water_mass, mul
             parcel_start, water_mass, multiplicity, dry_volume, kappa, f_org, critical_volume,
             c_state, w_mid, c_profile, consts,
             None if is_default(descriptor) and not general else descriptor)
-    if requests is None:
+    if requests is None and chem is None:
         engine.call_parcel("sdm_parcel_run", *args)
         return
-    sizes = {"moment_0": requests.n_moments, "moments": requests.n_moments,
-             "spectrum": requests.n_bins, "dv": 1}
-    engine.call_parcel_diag("sdm_parcel_run_diag", *args, requests,
-                            _diag_struct(engine, diag, sizes, n_steps * n_parcel))
+    c_diag = None
+    if requests is not None:
+        sizes = {"moment_0": requests.n_moments, "moments": requests.n_moments,
+                 "spectrum": requests.n_bins, "dv": 1}
+        c_diag = _diag_struct(engine, diag, sizes, n_steps * n_parcel)
+    if chem is None:
+        engine.call_parcel_diag("sdm_parcel_run_diag", *args, requests, c_diag)
+        return
+    engine.call_parcel_chem(
+        "sdm_parcel_run_chem", args[0], chem["cfg"], *args[1:], requests, c_diag,
+        chem["kappa_times_dry_volume"], chem["moles"], chem["pH"], chem["do_chemistry_flag"],
+        chem["mixing_ratios"], chem["consts"], float(chem["dry_factor"]),
+        *(chem.get("counters") or (None, None, None)),
+        _chem_profile_struct(engine, chem.get("profile"), n_steps * n_parcel))
+
+
+def _chem_profile_struct(engine, profile, n_rows):
+    """abi.ParcelChemProfile of a dict of engine arrays (None: no record)"""
+    if profile is None:
+        return None
+    out = abi.ParcelChemProfile()
+
+    def address(array, dtype):
+        if array is not None and engine.size(array) != n_rows:
+            raise ValueError(f"parcel: a chemistry profile member must hold {n_rows} values")
+        return _address(array, dtype) or 0
+
+    for g, array in enumerate(profile.get("mixing_ratio") or [None] * 6):
+        out.mixing_ratio[g] = address(array, FLOAT)
+    for a, array in enumerate(profile.get("aq_total") or [None] * 7):
+        out.aq_total[a] = address(array, FLOAT)
+    out.n_flagged = address(profile.get("n_flagged"), INT) or None
+    out.dv = address(profile.get("dv"), FLOAT) or None
+    return out
+
+
+def diag_sum(multiplicity, values):
+    """the SUM of include/sdm_parcel_diag.h of multiplicity * values on the host, add for add"""
+    terms = np.asarray(multiplicity).astype(float) * np.asarray(values, dtype=float)
+    padded = np.zeros(-(-max(terms.size, 1) // _DIAG_LANES) * _DIAG_LANES)
+    padded[:terms.size] = terms  # (+0.0 added to a partial that started at +0.0 changes no bit)
+    partial = np.zeros(_DIAG_LANES)
+    for chunk in padded.reshape(-1, _DIAG_LANES):
+        partial = partial + chunk
+    stride = _DIAG_LANES // 2
+    while stride >= 1:
+        partial[:stride] = partial[:stride] + partial[stride:2 * stride]
+        stride //= 2
+    return float(partial[0])
 
 
 def _diag_struct(engine, diag, sizes, n_rows):
@@ -162,7 +216,8 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
 
     def __init__(self, engine, formulae, setup, *, dt, T0, p0, qv0, w, mass_of_dry_air, z0=0,
                  counts, multiplicity, water_mass, dry_volume, kappa, f_org=None, route="fused",
-                 steps_per_launch=0, general=False):
+                 steps_per_launch=0, general=False, chemistry=None, mole_fractions=None,
+                 dry_rho=None, dry_molar_mass=None, initial_moles=None, molar_mass=None):
         if route not in ROUTES:
             raise ValueError(f"route must be one of {ROUTES}, not {route!r}")
         check_hydrostatics(formulae)
@@ -184,6 +239,21 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
                 "CondensationRunner with a Population")
         if setup.dt_cond_range[0] == 0:
             raise NotImplementedError("dt_cond_range[0] == 0")
+        self.chemistry = chemistry
+        if chemistry is not None:
+            if self.descriptor.option[_SGM] != 0:
+                raise NotImplementedError(
+                    "parcel with chemistry: a surface tension other than Constant is not served "
+                    "(the organic fraction would have to follow the dry volume)")
+            if mole_fractions is None or dry_rho is None or dry_molar_mass is None:
+                raise ValueError("parcel with chemistry needs mole_fractions, dry_rho and "
+                                 "dry_molar_mass")
+            if route == "fused" and engine.parcel_chem_library is None:
+                raise NotImplementedError(
+                    f"engine `{engine.name}` has no library for the parcel with aqueous "
+                    "chemistry: route='fused' is not available on it (route='stages' is)")
+            if engine.chemistry_library is None:
+                raise NotImplementedError(f"engine `{engine.name}` has no chemistry library")
         self.route, self.general = route, bool(general)
         self.dt = float(dt)
         self.cfg = parcel_cfg(formulae, setup, self.dt, steps_per_launch)
@@ -238,12 +308,58 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
                             float)
         self.f_org = column(np.zeros(n_sd) if f_org is None else f_org, "f_org", float)
         self.critical_volume = engine.full(n_sd, FLOAT, np.nan)
+        if chemistry is not None:
+            self._init_chemistry(mole_fractions, dry_rho, dry_molar_mass, initial_moles,
+                                 molar_mass, np.ascontiguousarray(dry_volume, dtype=float),
+                                 np.broadcast_to(np.asarray(kappa, dtype=float), (n_sd,)))
+        self.last_chem_profile = None
         self.n_steps = 0  # time steps asked for so far: the clock of w(t)
         self.last_profile = None
         self.last_products = None
         self.last_rows = None
         self.diag_fill = np.nan  # what the rows of steps a failed parcel did not carry out hold
         self._reported = set()
+
+    def _init_chemistry(self, mole_fractions, dry_rho, dry_molar_mass, initial_moles, molar_mass,
+                        dry_volume, kappa):
+        """the columns of the third dynamic: ammonium bisulphate (moles_S_VI = moles_N_mIII =
+        vdry * dry_rho / dry_molar_mass, the others 0) unless `initial_moles` ({key: column})
+        says otherwise, pH = pH_w, the flag clear, mixing ratios from the mole fractions"""
+        eng, formulae, n_sd, n_parcel = self.engine, self.formulae, self.n_sd, self.n_parcel
+        chem.check_formulae(formulae, molar_mass)
+        self.dry_factor = float(dry_molar_mass) / float(dry_rho)
+        self.chem_cfg = self.chemistry.cfg(formulae, self.dt, 0.0)  # (dv: per step)
+        self.chem_consts = chem.constants_of(formulae, molar_mass)
+        salt = dry_volume * float(dry_rho) / float(dry_molar_mass)
+        unknown = set(initial_moles or {}) - set(chem.AQUEOUS)
+        if unknown:
+            raise ValueError(f"initial_moles of {sorted(unknown)}: the keys are {chem.AQUEOUS}")
+        self.moles = []
+        for key in chem.AQUEOUS:
+            column = salt if key in ("S_VI", "N_mIII") else np.zeros(n_sd)
+            if initial_moles and key in initial_moles:
+                column = np.broadcast_to(np.asarray(initial_moles[key], dtype=float), (n_sd,))
+            self.moles.append(eng.upload(np.ascontiguousarray(column, dtype=float).copy()))
+        self.kappa_times_dry_volume = eng.upload(np.ascontiguousarray(kappa * dry_volume))
+        self.pH = eng.full(n_sd, FLOAT, float(chem._constant(formulae, "pH_w")))  # pylint: disable=protected-access
+        self.do_chemistry_flag = eng.zeros(n_sd, np.uint8)
+        ratios = chem.mixing_ratios_of(mole_fractions, formulae, molar_mass)
+        self.mixing_ratios = [eng.upload(np.broadcast_to(np.asarray(ratios[g], dtype=float),
+                                                         (n_parcel,)).copy())
+                              for g in chem.GASES]
+        self.chem_counters = [eng.zeros(n_parcel, INT) for _ in CHEM_COUNTERS]
+
+    def _chem_record(self, n_rows):
+        eng = self.engine
+        return {"mixing_ratio": [eng.full(n_rows, FLOAT, np.nan) for _ in chem.GASES],
+                "aq_total": [eng.full(n_rows, FLOAT, np.nan) for _ in chem.AQUEOUS],
+                "n_flagged": eng.full(n_rows, INT, -1), "dv": eng.full(n_rows, FLOAT, np.nan)}
+
+    def _chem_call(self, record):
+        return {"cfg": self.chem_cfg, "kappa_times_dry_volume": self.kappa_times_dry_volume,
+                "moles": self.moles, "pH": self.pH, "do_chemistry_flag": self.do_chemistry_flag,
+                "mixing_ratios": self.mixing_ratios, "consts": self.chem_consts,
+                "dry_factor": self.dry_factor, "counters": self.chem_counters, "profile": record}
 
     # ---- construction from a spectrum ---------------------------------------------------------
     @classmethod
@@ -364,7 +480,9 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
         pysdm_amd.products objects, or a RequestTable) it returns (profile, {product name: array
         of n_steps x n_parcel (x n_bins)}): the products of the state after every step (NaN for
         steps a failed parcel did not carry out); the evaluated table itself is kept in
-        `last_rows`.  Raises
+        `last_rows`.  With chemistry the chemistry profile ({"mixing_ratio": 6 x n_steps x
+        n_parcel, "aq_total": 7 x ..., "n_flagged", "dv"}, kept in `last_chem_profile`) comes
+        second: (profile, chemistry profile) or (profile, chemistry profile, products).  Raises
         RuntimeError("Condensation failed", parcel, step) after the call for the first parcel whose
         solver failed in it: the other parcels' state stays valid (and the profile is kept in
         `last_profile`); a failed parcel is skipped from then on"""
@@ -376,6 +494,9 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
         table = self._table(products) if isinstance(products, RequestTable) or len(products) \
             else None
         diag = None
+        chem_record = None
+        if n_steps > 0 and self.chemistry is not None:
+            chem_record = self._chem_record(n_steps * n_parcel)
         if n_steps > 0:
             w_mid = self.w_mid(n_steps)
             if table is not None:
@@ -394,9 +515,10 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
                             critical_volume=self.critical_volume, state=self.state,
                             w_mid=eng.upload(w_mid.reshape(-1)), profile=record,
                             descriptor=self.descriptor, general=self.general,
-                            requests=None if table is None else table.c_struct(), diag=diag)
+                            requests=None if table is None else table.c_struct(), diag=diag,
+                            chem=None if self.chemistry is None else self._chem_call(chem_record))
             else:
-                self._run_stages(w_mid, record, table, diag)
+                self._run_stages(w_mid, record, table, diag, chem_record)
             self.n_steps += n_steps
         out = None
         if record is not None:
@@ -411,11 +533,25 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
             if not profile:
                 out = None
         self.last_profile, self.last_products = out, values
+        chem_out = None
+        if self.chemistry is not None:
+            shape = (n_steps, n_parcel)
+            get = lambda a: eng.download(a).reshape(shape)  # noqa: E731
+            if chem_record is None:
+                chem_record = {"mixing_ratio": [eng.empty(0, FLOAT)] * 6,
+                               "aq_total": [eng.empty(0, FLOAT)] * 7,
+                               "n_flagged": eng.empty(0, INT), "dv": eng.empty(0, FLOAT)}
+            chem_out = {"mixing_ratio": np.stack([get(a) for a in chem_record["mixing_ratio"]]),
+                        "aq_total": np.stack([get(a) for a in chem_record["aq_total"]]),
+                        "n_flagged": get(chem_record["n_flagged"]), "dv": get(chem_record["dv"])}
+            self.last_chem_profile = chem_out
         failed = eng.download(self.state["failed_step"])
         for parcel in np.flatnonzero(failed >= 0):
             if int(parcel) not in self._reported:
                 self._reported.update(int(p) for p in np.flatnonzero(failed >= 0))
                 raise RuntimeError("Condensation failed", int(parcel), int(failed[parcel]))
+        if self.chemistry is not None:
+            return (out, chem_out) if table is None else (out, chem_out, values)
         return out if table is None else (out, values)
 
     def _latent_heat(self, T, scratch):
@@ -434,7 +570,7 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
             return const.l_tri * float(eng.download(scratch)[0])
         return const.l_tri + (const.c_pv - const.c_pw) * (T - const.T_tri)
 
-    def _run_stages(self, w_mid, record, table=None, diag=None):  # pylint: disable=too-many-locals,too-many-statements
+    def _run_stages(self, w_mid, record, table=None, diag=None, chem_record=None):  # pylint: disable=too-many-locals,too-many-statements
         """the time step of include/sdm_parcel.h with the stage symbols, parcel after parcel; the
         products' table with `sdm_parcel_diagnose` on the parcel's slice after each step"""
         eng, const, cfg, setup = self.engine, self.formulae.constants, self.cfg, self.setup
@@ -459,6 +595,13 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
         identity = eng.upload(np.arange(most, dtype=np.int64))
         dt_range = (setup.dt_cond_range[0], min(setup.dt_cond_range[1], self.dt))
         n_parcel = self.n_parcel
+        with_chem = self.chemistry is not None
+        if with_chem:
+            chem_cfg = abi.ChemistryCfg.from_buffer_copy(self.chem_cfg)
+            chem_cfg.timestep = self.dt
+            counts = eng.zeros(3, INT)
+            chem_rows = {name: ([eng.download(a) for a in value] if isinstance(value, list)
+                                else eng.download(value)) for name, value in chem_record.items()}
         for c in range(n_parcel):
             if host["failed_step"][c] >= 0:
                 continue
@@ -527,6 +670,31 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
                 for name, row in rows.items():
                     if row is not None:
                         row[k * n_parcel + c] = host[name][c]
+                if with_chem:  # points 2-5 of include/sdm_parcel_chem.h with the stage symbols
+                    at = k * n_parcel + c
+                    chem_cfg.cell_volume = dv
+                    ratios = [mr[c:c + 1] for mr in self.mixing_ratios]
+                    eng.call("sdm_volume_of_water_mass", v_wet[:n], mass, n, float(const.rho_w))
+                    eng.call_chemistry(
+                        "sdm_chemistry_step", chem_cfg, n, 1, identity[:n], cell_start, cell[:n],
+                        self.multiplicity[r0:r1], v_wet[:n], [m[r0:r1] for m in self.moles],
+                        self.pH[r0:r1], self.do_chemistry_flag[r0:r1], one["T"], one["p"],
+                        one["prhod"], ratios, counts, self.chem_consts)
+                    for counter, count in zip(self.chem_counters, eng.download(counts)):
+                        counter[c:c + 1] += int(count)
+                    sulphate = self.moles[chem.AQUEOUS.index("S_VI")][r0:r1]
+                    eng.assign(self.dry_volume[r0:r1], sulphate * self.dry_factor)
+                    eng.assign(self.kappa[r0:r1],
+                               self.kappa_times_dry_volume[r0:r1] / self.dry_volume[r0:r1])
+                    mult = eng.download(self.multiplicity[r0:r1])
+                    for g in range(6):
+                        chem_rows["mixing_ratio"][g][at] = eng.download(ratios[g])[0]
+                    for a in range(7):
+                        chem_rows["aq_total"][a][at] = diag_sum(
+                            mult, eng.download(self.moles[a][r0:r1]))
+                    chem_rows["n_flagged"][at] = int(np.count_nonzero(
+                        eng.download(self.do_chemistry_flag[r0:r1])))
+                    chem_rows["dv"][at] = dv
                 if table is not None:
                     at = k * n_parcel + c
                     diagnose_call(eng, self.formulae, requests, parcel_start=cell_start,
@@ -540,6 +708,11 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
                         diag_rows[name][at * width:(at + 1) * width] = eng.download(array)
         for name, row in diag_rows.items():
             eng.assign(diag[name], eng.upload(row))
+        if with_chem:
+            for name, value in chem_rows.items():
+                for dst, src in (zip(chem_record[name], value) if isinstance(value, list)
+                                 else ((chem_record[name], value),)):
+                    eng.assign(dst, eng.upload(src))
         for name, array in self.state.items():
             eng.assign(array, eng.upload(host[name]))
         for name, row in rows.items():
@@ -549,12 +722,26 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
     # ---- state --------------------------------------------------------------------------------------
     def snapshot(self):
         """host copies of everything a later `restore` needs: the parcels' state arrays, the
-        per-droplet water masses and critical volumes, and the clock of w(t)"""
+        per-droplet water masses and critical volumes, and the clock of w(t); with chemistry also
+        the dry volumes, kappa, the seven amounts, pH, the flag, the mixing ratios and the three
+        counters"""
         down = self.engine.download
         out = {name: down(array) for name, array in self.state.items()}
         out["water_mass"] = down(self.water_mass)
         out["critical_volume"] = down(self.critical_volume)
         out["n_steps"] = self.n_steps
+        if self.chemistry is not None:
+            out.update(self._chem_columns(down))
+        return out
+
+    def _chem_columns(self, get=lambda array: array):
+        """the columns chemistry adds to a snapshot, by name (`get` applied to every array)"""
+        out = {"dry_volume": get(self.dry_volume), "kappa": get(self.kappa), "pH": get(self.pH),
+               "do_chemistry_flag": get(self.do_chemistry_flag)}
+        out.update({f"moles_{key}": get(array) for key, array in zip(chem.AQUEOUS, self.moles)})
+        out.update({f"mixing_ratio_{gas}": get(array)
+                    for gas, array in zip(chem.GASES, self.mixing_ratios)})
+        out.update({name: get(array) for name, array in zip(CHEM_COUNTERS, self.chem_counters)})
         return out
 
     def restore(self, state):
@@ -566,11 +753,14 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
             if name == "n_steps":
                 self.n_steps = int(value)
                 continue
-            target = {"water_mass": self.water_mass,
-                      "critical_volume": self.critical_volume}.get(name, self.state.get(name))
+            columns = {"water_mass": self.water_mass, "critical_volume": self.critical_volume}
+            if self.chemistry is not None:
+                columns.update(self._chem_columns())
+            target = columns.get(name, self.state.get(name))
             if target is None:
                 raise KeyError(name)
-            dtype = INT if name in _INT_FIELDS else FLOAT
+            dtype = INT if name in _INT_FIELDS + CHEM_COUNTERS else \
+                np.uint8 if name == "do_chemistry_flag" else FLOAT
             value = np.ascontiguousarray(np.broadcast_to(
                 np.asarray(value, dtype=dtype), (eng.size(target),)))
             eng.assign(target, eng.upload(value))

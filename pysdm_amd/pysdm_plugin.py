@@ -514,6 +514,14 @@ def run_parcel(particulator, steps, products=()):
     environment's current values and the previous ones that `sync_parcel_vars` reads next, the
     dynamic's counters, `rh_max` and `success`, and `n_steps`.
 
+    It also serves the dynamics `AmbientThermodynamics`, `Condensation`, `AqueousChemistry`,
+    registered in that order (`sdm_parcel_run_chem`, include/sdm_parcel_chem.h): the `moles_*`
+    attributes are marked updated (their dependants `conc_*`, `pH`, `dry volume` and `kappa`
+    follow), the dynamic's `do_chemistry_flag` is the particulator's own and its
+    `environment_mixing_ratios` are written back; what the reference asserts on (a pH solve that
+    does not converge, a negative amount, a gas taken beyond what the parcel holds) raises
+    afterwards.  Any other set of dynamics is refused.
+
     Observers and PySDM's own product objects are NOT notified per step.  `products` (objects of
     pysdm_amd.products, which carry PySDM's names, arguments and units) are evaluated inside the
     kernel's step loop after every step (`sdm_parcel_run_diag`, include/sdm_parcel_diag.h).
@@ -526,7 +534,10 @@ def run_parcel(particulator, steps, products=()):
     env = particulator.environment
     if type(env).__name__ != "Parcel":
         raise ValueError(f"run_parcel needs a Parcel environment, not {type(env).__name__}")
-    if sorted(particulator.dynamics) != ["AmbientThermodynamics", "Condensation"]:
+    with_chem = list(particulator.dynamics) == ["AmbientThermodynamics", "Condensation",
+                                                "AqueousChemistry"]
+    if not with_chem and sorted(particulator.dynamics) != ["AmbientThermodynamics",
+                                                           "Condensation"]:
         raise ValueError("run_parcel needs exactly the dynamics AmbientThermodynamics and "
                          f"Condensation, not {sorted(particulator.dynamics)}")
     if "a_w_ice" in env.variables:
@@ -587,8 +598,36 @@ def run_parcel(particulator, steps, products=()):
         diag = {name: eng.full(steps * size, FLOAT, np.nan) for name, size in
                 (("moment_0", table.n_moments), ("moments", table.n_moments),
                  ("spectrum", table.n_bins), ("dv", 1)) if size > 0}
+    chem_call = None
+    if with_chem:
+        from . import chemistry as _chem  # pylint: disable=import-outside-toplevel
+
+        aqueous = particulator.dynamics["AqueousChemistry"]
+        if eng.parcel_chem_library is None:
+            raise NotImplementedError(
+                f"engine `{eng.name}` has no library for the parcel with aqueous chemistry")
+        if descriptor.option[_parcel._SGM] != 0:  # pylint: disable=protected-access
+            raise ValueError("run_parcel with AqueousChemistry needs the Constant surface tension")
+        chem_setup = _chem.ChemistrySetup(
+            aqueous.system_type, aqueous.n_substep,
+            ionic_strength_threshold=aqueous.ionic_strength_threshold,
+            pH_H_min=aqueous.pH_H_min, pH_H_max=aqueous.pH_H_max, pH_rtol=aqueous.pH_rtol)
+        # (the pH attribute's own storage, not its getter: reading it would run a solve)
+        acidity = getattr(attrs, _PRIVATE + "attributes")["pH"]
+        ratios = [eng.upload(np.ascontiguousarray(aqueous.environment_mixing_ratios[gas],
+                                                  dtype=float).reshape(1))
+                  for gas in _chem.GASES]
+        chem_counters = [eng.zeros(1, INT) for _ in range(3)]
+        chem_call = {
+            "cfg": chem_setup.cfg(formulae, dt, 0.0),
+            "kappa_times_dry_volume": attrs["kappa times dry volume"].data,
+            "moles": [attrs[f"moles_{key}"].data for key in _chem.AQUEOUS],
+            "pH": acidity.data.data, "do_chemistry_flag": aqueous.do_chemistry_flag.data,
+            "mixing_ratios": ratios, "consts": _chem.constants_of(formulae),
+            "dry_factor": float(aqueous.dry_molar_mass) / float(aqueous.dry_rho),
+            "counters": chem_counters, "profile": None}
     _parcel.parcel_call(
-        eng, formulae, cfg, n_steps=steps,
+        eng, formulae, cfg, n_steps=steps, chem=chem_call,
         parcel_start=eng.upload(np.array([0, n_sd], dtype=np.int64)),
         water_mass=attrs["signed water mass"].data, multiplicity=attrs["multiplicity"].data,
         dry_volume=attrs["dry volume"].data, kappa=attrs["kappa"].data,
@@ -597,6 +636,16 @@ def run_parcel(particulator, steps, products=()):
         profile=record, descriptor=descriptor,
         requests=None if table is None else table.c_struct(), diag=diag)
     attrs.mark_updated("signed water mass")
+    if with_chem:
+        for key in _chem.AQUEOUS:
+            attrs.mark_updated(f"moles_{key}")
+        for gas, ratio in zip(_chem.GASES, ratios):
+            aqueous.environment_mixing_ratios[gas][:] = eng.download(ratio)
+        # the dynamic's per-cell constants as its last call left them (the temperature after the
+        # last step): the `pH` attribute's next solve reads them
+        particulator.backend.chem_recalculate_cell_data(
+            equilibrium_consts=aqueous.equilibrium_consts, kinetic_consts=aqueous.kinetic_consts,
+            temperature=current["T"])
     done = int(eng.download(state["steps_done"])[0])
     rows = {name: eng.download(array) for name, array in record.items()}
     # what notify() leaves behind: _tmp holds the values before the last step carried out
@@ -616,6 +665,8 @@ def run_parcel(particulator, steps, products=()):
     if done < steps:
         eng.fill(dynamic.success.data, False)
         raise RuntimeError("Condensation failed")
+    if with_chem:
+        _chem.raise_if_counted([int(eng.download(c)[0]) for c in chem_counters])
     if table is None:
         return rows
     from .products import Rows  # pylint: disable=import-outside-toplevel

@@ -24,6 +24,13 @@ existed before: `run(1)`, `snapshot()` and `diagnostics.moments` / `spectrum_mom
 the five unfiltered products and the spectrum only).  `--products-stepwise-only` times just the
 latter, which needs nothing of this module's newer interfaces.  Writes
 profiles/parcel_products_timing.json.
+
+`--chemistry` is a further measurement of its own: the parcel with aqueous chemistry
+(include/sdm_parcel_chem.h), PySDM's default formulae, n_substep = 5, an open and a closed system:
+the fused route (`sdm_parcel_run_chem`: per step one launch of the parcel kernel and one of
+k_parcel_chem) at 1, 16, 256 and 1024 parcels, the stage route (the stage step, then
+`sdm_chemistry_step` on the parcel's slice and the two element-wise updates) at 1 and 16, and the
+same ascents without chemistry on the same build.  Writes profiles/parcel_chem_timing.json.
 """
 import argparse
 import json
@@ -39,7 +46,14 @@ STAGE_SIZES = (1, 16)
 N_SD, STEPS, DT = 256, 100, 1.0
 
 
-def make_runner(kind, n_parcel, route, steps_per_launch, engine=None):
+CHEM_SUBSTEPS = 5
+# ammonium bisulphate and the trace gases of the reference's Kreidenweis et al. 2003 example
+CHEM_DRY_RHO, CHEM_DRY_MOLAR_MASS = 1800.0, 0.11511
+CHEM_MOLE_FRACTIONS = {"SO2": 0.2e-9, "O3": 50e-9, "H2O2": 0.5e-9, "CO2": 360e-6, "HNO3": 0.1e-9,
+                       "NH3": 0.1e-9}
+
+
+def make_runner(kind, n_parcel, route, steps_per_launch, engine=None, system=None):
     from pysdm_amd import spectra  # pylint: disable=import-outside-toplevel
     from pysdm_amd.condensation import CondensationSetup  # pylint: disable=import-outside-toplevel
     from pysdm_amd.engine import HipEngine  # pylint: disable=import-outside-toplevel
@@ -47,12 +61,19 @@ def make_runner(kind, n_parcel, route, steps_per_launch, engine=None):
     from tests.parcel_cases import formulae_of  # pylint: disable=import-outside-toplevel
 
     updrafts = np.linspace(0.2, 5.0, n_parcel) if n_parcel > 1 else np.array([2.0])
+    chemistry = {}
+    if system is not None:
+        from pysdm_amd.chemistry import ChemistrySetup  # pylint: disable=import-outside-toplevel
+
+        chemistry = dict(chemistry=ChemistrySetup(system, CHEM_SUBSTEPS),
+                         mole_fractions=CHEM_MOLE_FRACTIONS, dry_rho=CHEM_DRY_RHO,
+                         dry_molar_mass=CHEM_DRY_MOLAR_MASS)
     return ParcelRunner.from_spectrum(
         engine or HipEngine.get(), formulae_of(kind), CondensationSetup(), dt=DT, T0=290.0,
         p0=100000.0, qv0=0.012, w=updrafts, mass_of_dry_air=1.0,
         spectrum=spectra.Lognormal(norm_factor=60e6 / 1.18, m_mode=0.04e-6, s_geom=1.4),
         kappa=1.28, f_org=None if kind == "default" else 0.3, n_sd=N_SD, n_parcel=n_parcel,
-        route=route, steps_per_launch=steps_per_launch)
+        route=route, steps_per_launch=steps_per_launch, **chemistry)
 
 
 def timed(runner, start, steps, reps, warmup, call=None):
@@ -182,6 +203,49 @@ def main_products(args):
     print("wrote", out)
 
 
+def measure_chemistry(system, n_parcel, route, reps, warmup):
+    """`system`: "open", "closed", or None for the same ascent without chemistry"""
+    runner = make_runner("default", n_parcel, route, 0, system=system)
+    start = runner.snapshot()
+    samples = timed(runner, start, STEPS, reps, warmup)
+    final = runner.snapshot()
+    assert (final["failed_step"] == -1).all() and (final["steps_done"] == STEPS).all()
+    ms = float(np.median(samples))
+    out = {"chemistry": system or "none", "route": route, "n_parcel": n_parcel,
+           "n_sd_per_parcel": N_SD, "steps": STEPS, "reps": reps, "ms_median": round(ms, 3),
+           "ms_min": round(float(np.min(samples)), 3), "ms_max": round(float(np.max(samples)), 3),
+           "ms_per_parcel_step": round(ms / (n_parcel * STEPS), 5)}
+    if system is not None:
+        out["n_substep"] = CHEM_SUBSTEPS
+        out["n_flagged_last"] = [int(v) for v in runner.last_chem_profile["n_flagged"][-1][
+            [0, -1]]] if runner.last_chem_profile is not None else None
+        out["counts"] = [int(final[name].sum()) for name in
+                         ("n_failed", "n_negative", "n_exceeded")]
+    return out
+
+
+def main_chemistry(args):
+    results = []
+    for system in (None, "open", "closed"):
+        for n_parcel in SIZES:
+            results.append(measure_chemistry(system, n_parcel, "fused", args.reps, args.warmup))
+            print(json.dumps(results[-1]), flush=True)
+        if system is not None:
+            for n_parcel in STAGE_SIZES:
+                results.append(measure_chemistry(system, n_parcel, "stages", args.reps,
+                                                 args.warmup))
+                print(json.dumps(results[-1]), flush=True)
+    out = args.out or os.path.join(ROOT, "profiles", "parcel_chem_timing.json")
+    with open(out, "w", encoding="utf-8") as handle:
+        handle.write(json.dumps({
+            "workload": f"{N_SD} super-droplets per parcel, {STEPS} steps of {DT} s, updrafts "
+                        f"0.2 .. 5 m/s (2 m/s for one parcel); PySDM's default formulae; "
+                        f"AqueousChemistry with n_substep = {CHEM_SUBSTEPS}; HIP events, median of "
+                        f"{args.reps} after {args.warmup} warm-up call(s)",
+            "results": results}, indent=1) + "\n")
+    print("wrote", out)
+
+
 def main():
     parser = argparse.ArgumentParser()
     parser.add_argument("--reps", type=int, default=5)
@@ -193,7 +257,12 @@ def main():
     parser.add_argument("--products", action="store_true",
                         help="time the products instead (see the module's docstring)")
     parser.add_argument("--products-stepwise-only", action="store_true")
+    parser.add_argument("--chemistry", action="store_true",
+                        help="time the parcel with aqueous chemistry instead (see the docstring)")
     args = parser.parse_args()
+    if args.chemistry:
+        main_chemistry(args)
+        return
     if args.products or args.products_stepwise_only:
         main_products(args)
         return
