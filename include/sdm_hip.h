@@ -106,7 +106,15 @@ const char *sdm_phase_name(int phase);
  *   LDS.
  * SDM_OPT_NARROW_STEP: 1 = inside a call of several steps (one cell, non-adaptive) the permutation
  *   goes from a step's pair kernel to the next step's shuffle build as int64_t; 0 (default) = as
- *   32-bit ids.  Nothing narrow is left in the state when a call returns.                        */
+ *   32-bit ids.  Nothing narrow is left in the state when a call returns.
+ * SDM_OPT_PAIR_TAGS: 1 = those 32-bit ids travel bare; 0 (default) = where they leave nine bits
+ *   free (n_sd < 2^21; one cell, non-adaptive, Golovin kernel without breakup, successor words,
+ *   ride-along sort), the pair kernel writes a class of the multiplicity and of the mass beside
+ *   each id, and the next step decides the pairs whose order is known from the classes and that
+ *   cannot collide without reading their state.  Results are the same bit for bit.  After a call
+ *   whose steps carried tags, control word 6 of sdm_step_state.ctl holds the pairs of tagged
+ *   steps whose state was not read (low 32 bits) and those whose state was (high 32 bits), each
+ *   saturating.                                                                                   */
 #define SDM_OPT_REC_FORMAT 3
 #define SDM_REC_FORMAT_AUTO 0
 #define SDM_REC_FORMAT_RECORDS 1
@@ -114,6 +122,7 @@ const char *sdm_phase_name(int phase);
 #define SDM_OPT_NO_CELL_COPY 5
 #define SDM_OPT_WALK_LOCAL 6
 #define SDM_OPT_NARROW_STEP 7
+#define SDM_OPT_PAIR_TAGS 8
 int sdm_ctx_set_option(sdm_ctx *ctx, int option, int64_t value);
 /* counters since the context was created / last cleared (host-side bookkeeping of the library):
  * re-sorts after a compaction done by the closed form; asked for and refused by the device; not

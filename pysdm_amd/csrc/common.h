@@ -62,10 +62,13 @@ struct sdm_ctx {
   int build_resident;      // index.hip: likewise k_bin_build2 (0: not asked yet, -1: unknown)
   // fused.hip: the pair kernel of the previous sub-step of this run sorted this one's events
   // (narrow: that kernel left the permutation as 32-bit ids in the buffer the next build reads)
+  // (tagged: ... with tags beside them, pair_tag.h)
   struct {
-    bool active, narrow;
+    bool active, narrow, tagged;
     const void *owner;
   } presorted;
+  // fused.hip: the steps of the current sdm_collision_run carry tags
+  bool tags_call;
   // fused.hip: which of the two sets of pair-list fill counts the previous step of the run left clean
   struct {
     bool active;
@@ -91,6 +94,7 @@ struct sdm_ctx {
   int opt_records, opt_no_presort, opt_no_cell_copy;  // SDM_OPT_REC_FORMAT / _NO_PRESORT / _NO_CELL_COPY
   int opt_no_walk_local;         // SDM_OPT_WALK_LOCAL
   int opt_wide_step;             // SDM_OPT_NARROW_STEP (1 = 64-bit permutation throughout)
+  int opt_no_pair_tags;          // SDM_OPT_PAIR_TAGS (1 = no tags beside the 32-bit ids)
   int64_t stats[SDM_N_STATS];    // SDM_STAT_* (host-side counters, sdm_ctx_read_stats)
   // fused.hip: what a multi-cell adaptive step knows at its end, for the next step of the same call
   // (valid length, an upper bound of the cell sizes; the state is sorted) - saves that step's

@@ -25,12 +25,13 @@ static int ctx_allocate(sdm_ctx *ctx) {
                         hipHostMallocMapped | hipHostMallocCoherent));
   memset(ctx->mailbox, 0, sizeof(int64_t) * SDM_MAILBOX_WORDS);
   if (const char *delay = getenv("SDM_DEBUG_BOX_DELAY_US")) ctx->debug_box_delay_us = atoi(delay);
-  // process-wide defaults of five A/B options (sdm_hip.h)
+  // process-wide defaults of six A/B options (sdm_hip.h)
   if (const char *fmt = getenv("SDM_REC_FORMAT")) ctx->opt_records = !strcmp(fmt, "records");
   ctx->opt_no_presort = getenv("SDM_NO_PRESORT") != nullptr;
   if (const char *copy = getenv("SDM_CELL_COPY")) ctx->opt_no_cell_copy = copy[0] == '0';
   if (const char *local = getenv("SDM_WALK_LOCAL")) ctx->opt_no_walk_local = local[0] == '0';
   if (const char *narrow = getenv("SDM_NARROW_STEP")) ctx->opt_wide_step = narrow[0] == '0';
+  if (const char *tags = getenv("SDM_PAIR_TAGS")) ctx->opt_no_pair_tags = tags[0] == '0';
   if (const char *shape = getenv("SDM_CELL_SHAPE")) {
     const int v = atoi(shape);
     if (v >= SDM_CELL_SHAPE_AUTO && v <= SDM_CELL_SHAPE_256) ctx->opt_cell_shape = v;
@@ -188,7 +189,7 @@ extern "C" int sdm_ctx_set_option(sdm_ctx *ctx, int option, int64_t value) {
   }
   if (option == SDM_OPT_REC_FORMAT || option == SDM_OPT_NO_PRESORT ||
       option == SDM_OPT_NO_CELL_COPY || option == SDM_OPT_WALK_LOCAL ||
-      option == SDM_OPT_NARROW_STEP) {
+      option == SDM_OPT_NARROW_STEP || option == SDM_OPT_PAIR_TAGS) {
     ARG_TRY(value == 0 || value == 1);
     // (a tile sort that rode in the last pair kernel, a sub-step launched ahead: both belong to
     // the format they were made for - none is pending between calls of a caller that changes it,
@@ -197,6 +198,7 @@ extern "C" int sdm_ctx_set_option(sdm_ctx *ctx, int option, int64_t value) {
     else if (option == SDM_OPT_NO_PRESORT) ctx->opt_no_presort = (int)value;
     else if (option == SDM_OPT_WALK_LOCAL) ctx->opt_no_walk_local = (int)value;
     else if (option == SDM_OPT_NARROW_STEP) ctx->opt_wide_step = (int)value;
+    else if (option == SDM_OPT_PAIR_TAGS) ctx->opt_no_pair_tags = (int)value;
     else ctx->opt_no_cell_copy = (int)value;
     ctx->presorted.active = false;
     ctx->build_resident = 0;  // (the occupancy of the build kernel depends on the format)

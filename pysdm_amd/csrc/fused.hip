@@ -23,6 +23,40 @@
 #include "index.h"
 #include "shuffle_build.h"
 #include "physics.h"
+#include "pair_tag.h"
+
+// ---- tags beside the ids (round 10; pair_tag.h): inside a call the Golovin pair kernel that sorts
+// ahead writes nine bits of bounds on {multiplicity, mass} next to each 32-bit id, the next build
+// carries them to the ends of the walks, and the next pair kernel decides most pairs - their order
+// and that they cannot collide - without the gather of the mirror records.
+// -DPAIR_TAGS=0 takes the code out, SDM_OPT_PAIR_TAGS = 1 / SDM_PAIR_TAGS=0 switch it off at run time.
+// Tuning builds: -DPAIR_TAG_PART=1 tags written and carried but never used, 2 the order within the
+// pair only, 3 (default) the full decision; -DPAIR_TAG_COUNT=0 without the two counts
+#ifndef PAIR_TAGS
+#define PAIR_TAGS 1
+#endif
+#ifndef PAIR_TAG_PART
+#define PAIR_TAG_PART 3
+#endif
+#ifndef PAIR_TAG_COUNT
+#define PAIR_TAG_COUNT 1
+#endif
+// FusedArgs::narrow, beside bits 0 and 1: the words written to `idx` carry tags | the words the
+// walks end at (and those of `idx_prev`) may carry tags
+#define NARROW_TAG_OUT 4
+#define NARROW_TAG_IN 8
+// ... and at the call's end: k_fold_counters folds the two counts and clears the references
+#define NARROW_TAG_FOLD 16
+// the call's references {n_ref, bits of the largest mass} (k_tag_ref): words of counter slot 0
+// that no counter uses - FusedArgs::slots is the pointer they are read through, and no kernel
+// argument moves
+#define TAG_N_REF 8
+#define TAG_M_MAX 9
+// words of a counter slot beyond the CNT_* kinds, and the control word they are folded into: pairs
+// of tagged steps whose gather was skipped (low 32 bits, saturating) and that gathered (high)
+#define SLOT_TAG_SKIPPED 6
+#define SLOT_TAG_GATHERED 7
+#define CTL_TAGS 6  // (one cell: k_max_cell's word of the multi-cell routes)
 
 int sdm_adaptive_end_async(sdm_ctx *ctx, const double *dt_left, int64_t n_cell,
                            const int64_t *cell_start, int64_t *scratch2, int64_t *end_dev);
@@ -118,8 +152,8 @@ struct FusedArgs {
   const void *rec;  // records of layout rec_fmt (shuffle_device.h: SDM_REC_*)
   int rec_fmt;
   // inside a call (one cell, non-adaptive, the next step's tile sort riding along): bit 0 = `idx`
-  // points to int32_t ids - the next build reads them so - bit 1 = `idx_prev` does.  (In what was
-  // padding: every other member lies where it lay)
+  // points to int32_t ids - the next build reads them so - bit 1 = `idx_prev` does; bits 2 and 3:
+  // NARROW_TAG_OUT, NARROW_TAG_IN.  (In what was padding: every other member lies where it lay)
   int narrow;
   const int32_t *ovf_head, *ovf_next;
   // successor words: events per tile of the build (shuffle_build.h) when the pair kernels take
@@ -195,6 +229,61 @@ __global__ void __launch_bounds__(SDM_CNT_SLOTS) k_fold_counters(FusedArgs A) {
     int64_t s = 0;
     for (int w = 0; w < SDM_CNT_SLOTS / SDM_WAVE; ++w) s += part[w][threadIdx.x];
     if (s != 0) counter_of(A, threadIdx.x)[0] += s;
+  }
+  if (PAIR_TAGS && (A.narrow & NARROW_TAG_FOLD)) {  // the call carried tags: its two counts, and the references cleared
+    __shared__ int64_t tpart[SDM_CNT_SLOTS / SDM_WAVE][2];
+    for (int w = 0; w < 2; ++w) {
+      const int64_t v = slot[SLOT_TAG_SKIPPED + w];
+      if (v != 0) slot[SLOT_TAG_SKIPPED + w] = 0;
+      const int64_t s = wave_sum_i64(v);
+      if (lane_id() == 0) tpart[threadIdx.x / SDM_WAVE][w] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      int64_t s[2] = {0, 0};
+      for (int w = 0; w < SDM_CNT_SLOTS / SDM_WAVE; ++w) { s[0] += tpart[w][0]; s[1] += tpart[w][1]; }
+      const int64_t cap = 0xffffffffll;
+      A.ctl[CTL_TAGS] = (s[0] < cap ? s[0] : cap) | ((s[1] < cap ? s[1] : cap) << 32);
+      A.slots[TAG_N_REF] = 0;
+      A.slots[TAG_M_MAX] = 0;
+    }
+  }
+}
+
+// the references of a call's tags (pair_tag.h): the largest multiplicity and the bits of the
+// largest positive mass over the super-droplets with multiplicity > 0, by atomic maximum into words
+// that are zero between calls - one atomic per word and workgroup.  (Positive doubles order like
+// their bit patterns; a NaN's pattern wins and pair_tag_m_base then answers 0: no mass class)
+__global__ void __launch_bounds__(SDM_BLOCK)
+k_tag_ref(const int64_t *__restrict__ multiplicity, const double *__restrict__ mass, int64_t n_sd,
+          int64_t *__restrict__ tag) {
+  static_assert(TAG_M_MAX == TAG_N_REF + 1 && TAG_M_MAX < SDM_CNT_STRIDE &&
+                    TAG_N_REF > SLOT_TAG_GATHERED && SLOT_TAG_SKIPPED >= CNT_KINDS,
+                "spare words of a counter slot");
+  __shared__ long long part[SDM_BLOCK / SDM_WAVE][2];
+  long long n_max = 0, m_max = 0;
+  for (int64_t i = TID(); i < n_sd; i += (int64_t)gridDim.x * SDM_BLOCK) {
+    const long long n = multiplicity[i], m = __double_as_longlong(mass[i]);
+    if (n > 0) {
+      n_max = n > n_max ? n : n_max;
+      m_max = m > m_max ? m : m_max;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    const long long n = __shfl_xor(n_max, o, 64), m = __shfl_xor(m_max, o, 64);
+    n_max = n > n_max ? n : n_max;
+    m_max = m > m_max ? m : m_max;
+  }
+  if (lane_id() == 0) {
+    part[threadIdx.x / SDM_WAVE][0] = n_max;
+    part[threadIdx.x / SDM_WAVE][1] = m_max;
+  }
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    long long v = 0;
+    for (int w = 0; w < SDM_BLOCK / SDM_WAVE; ++w) v = part[w][threadIdx.x] > v ? part[w][threadIdx.x] : v;
+    if (v > 0) atomicMax((long long *)&tag[TAG_N_REF + threadIdx.x], v);
   }
 }
 
@@ -546,12 +635,27 @@ struct WalkSeg {
   uint32_t seg_first, seg_len, n0, n1;
 };
 
+// what a tag-aware caller hands to pair_prob_body and gets back (pair_tag.h)
+struct PairTags {
+  double u;         // in: the slot's `rand`
+  uint32_t tj, tk;  // the tags the walks ended at, in the order of R.j, R.k
+  bool skipped;     // order and "no collision" decided from the tags: nothing was gathered
+  double mj, mk;    // masses of R.j, R.k as gathered (not skipped)
+};
+
 // pairing (find_pairs + sort_within_pair), kernel, probability, [Ec, fragment mass], [optimal dt]
 // for pair slot d; `u_b` = the slot's draw of the breakup streams
-template <int KERNEL, bool BREAKUP>
+// TAGS (Golovin, coalescence, one cell): the words the walks end at may carry tags
+// (NARROW_TAG_IN); with T and NARROW_TAG_OUT the slot's store is left to the caller, who writes it
+// with the tags of the state after the update
+template <int KERNEL, bool BREAKUP, bool TAGS = false>
 __device__ __forceinline__ PairInfo pair_prob_body(const sdm_step_cfg &cfg, const FusedArgs &A,
                                                    int64_t d, int64_t W, double u_b,
-                                                   const WalkSeg *L = nullptr) {
+                                                   const WalkSeg *L = nullptr,
+                                                   PairTags *T = nullptr) {
+  constexpr bool tags = TAGS && PAIR_TAGS && NARROW_IDX;
+  const bool tag_in = tags && (A.narrow & NARROW_TAG_IN);
+  const bool tag_out = tags && T && (A.narrow & NARROW_TAG_OUT);
   PairInfo R;
   R.have = false; R.off = 2; R.j = R.k = R.nj = R.nk = R.cid_j = 0;
   R.prob = 0.0; R.dt_optimal = INFINITY;
@@ -574,6 +678,16 @@ __device__ __forceinline__ PairInfo pair_prob_body(const sdm_step_cfg &cfg, cons
           if (p < W) id = walk_id(A.rec, A.rec_fmt, A.ovf_head, A.ovf_next, (int32_t)p, 0);
           else if (p < cfg.n_sd) id = idx_load(A.idx_prev, A.narrow & 2, p);
           else continue;
+          // (a tagged word passes through as it is - the state did not change - unless this step
+          // writes none: the last step of a call strips the tag)
+          if (tag_in && !(A.narrow & NARROW_TAG_OUT)) id &= PAIR_TAG_ID_MASK;
+          // (... and the first tagging step of a call gives the unpaired position its tag: one
+          // gather per launch, or the super-droplet's next pair would have to gather for it)
+          if (tags && !tag_in && (A.narrow & NARROW_TAG_OUT) && p < W && id < cfg.n_sd) {
+            const SD s = sd_load(cfg, A, id, false);
+            id |= (int64_t)pair_tag_encode(s.n, s.m, A.slots[TAG_N_REF],
+                                           pair_tag_m_base(A.slots[TAG_M_MAX])) << PAIR_TAG_SHIFT;
+          }
           if (NARROW_IDX && (A.narrow & 1)) ((int32_t *)A.idx)[p] = (int32_t)id;
           else A.idx[p] = id;
         }
@@ -599,6 +713,41 @@ __device__ __forceinline__ PairInfo pair_prob_body(const sdm_step_cfg &cfg, cons
   R.off = (uint8_t)(i - 2 * d);
   const bool traced = A.rec != nullptr;
   int64_t j = traced ? tj : A.idx[i], k = traced ? tk : A.idx[i + 1];
+  if (tag_in) {  // word = id | tag << PAIR_TAG_SHIFT
+    uint32_t tag_j = (uint32_t)j >> PAIR_TAG_SHIFT, tag_k = (uint32_t)k >> PAIR_TAG_SHIFT;
+    j &= PAIR_TAG_ID_MASK;
+    k &= PAIR_TAG_ID_MASK;
+    if (tag_out && PAIR_TAG_PART >= 2) {
+      // the order within the pair from the classes (a higher class is a strictly smaller
+      // multiplicity): the exchange is made here, and `swap` below - should the pair gather after
+      // all - finds nothing left to do
+      const int order = pair_tag_order(tag_j, tag_k);
+      if (order == 1) {
+        const int64_t t = j; j = k; k = t;
+        const uint32_t tt = tag_j; tag_j = tag_k; tag_k = tt;
+      }
+      bool skip = false;
+      if (PAIR_TAG_PART >= 3 && order >= 0 && pair_tag_mc(tag_j) != 0 && pair_tag_mc(tag_k) != 0) {
+        // the probability's upper bound, by the probability's own arithmetic (monotone in every
+        // argument for kernel_param[0] >= 0, rho_w > 0, dt / dv >= 0: the enable logic)
+        const int64_t n_ref = A.slots[TAG_N_REF];
+        const double m_base = pair_tag_m_base(A.slots[TAG_M_MAX]);
+        SD bj, bk;
+        bj.n = pair_tag_n_ub(tag_j, n_ref); bj.m = pair_tag_m_ub(tag_j, m_base);
+        bk.n = 0; bk.m = pair_tag_m_ub(tag_k, m_base);
+        bj.r = bj.u = bk.r = bk.u = 0.0;
+        double p_ub = pair_prob_value<KERNEL>(cfg, A, d, bj, bk);
+        if (p_ub != 0) p_ub /= (double)cfg.substeps;
+        skip = pair_tag_no_collision(p_ub, T->u);
+      }
+      if (skip) {  // gamma is zero in the full computation too: the ids in their order, nothing else
+        T->skipped = true;
+        T->tj = tag_j; T->tk = tag_k;
+        R.j = j; R.k = k;
+        return R;
+      }
+    }
+  }
   const bool need_r = KERNEL == SDM_KERNEL_GEOMETRIC || KERNEL == SDM_KERNEL_PARAMETERIZED ||
                       KERNEL == SDM_KERNEL_SIMPLE_GEOMETRIC;
   SD sj = sd_load(cfg, A, j, need_r), sk = sd_load(cfg, A, k, need_r);
@@ -610,7 +759,10 @@ __device__ __forceinline__ PairInfo pair_prob_body(const sdm_step_cfg &cfg, cons
     const int64_t tn = nj; nj = nk; nk = tn;
     const SD ts = sj; sj = sk; sk = ts;
   }
-  if (NARROW_IDX && (A.narrow & 1)) {  // (traced, one cell: i = 2d - one 8-byte store per slot)
+  if (tag_out) {  // (the caller stores the slot, after the update)
+    T->mj = sj.m;
+    T->mk = sk.m;
+  } else if (NARROW_IDX && (A.narrow & 1)) {  // (traced, one cell: i = 2d - one 8-byte store per slot)
     *(int2 *)((int32_t *)A.idx + i) = make_int2((int32_t)j, (int32_t)k);
   } else if (swap || traced) {
     A.idx[i] = j;
@@ -871,8 +1023,13 @@ __device__ __forceinline__ int pair_update_body(const sdm_step_cfg &cfg, const F
 }
 
 // ---- non-adaptive: everything about a pair in one kernel -------------------------------------
+// (the instantiation that takes the ids out of tagged words asks for the 8 waves per SIMD it had
+// without that: left alone it takes 106 SGPRs and 7.  The others ask for what is theirs anyway)
+#define PAIR_ALL_TAGS(K, B, C) (PAIR_TAGS && NARROW_IDX && (K) == SDM_KERNEL_GOLOVIN && !(B) && !(C))
 template <int KERNEL, bool BREAKUP, bool CLOSED = false>
-__global__ void __launch_bounds__(SDM_BLOCK) k_pair_all(sdm_step_cfg cfg, FusedArgs A) {
+__global__ void __launch_bounds__(SDM_BLOCK)
+__attribute__((amdgpu_waves_per_eu(PAIR_ALL_TAGS(KERNEL, BREAKUP, CLOSED) ? 8 : 1, 8)))
+k_pair_all(sdm_step_cfg cfg, FusedArgs A) {
   VELOCITY_LAW_PROMISE(CLOSED);
   __shared__ u128 lds[2];
   const int64_t W = A.ctl[CTL_WORK];
@@ -886,7 +1043,10 @@ __global__ void __launch_bounds__(SDM_BLOCK) k_pair_all(sdm_step_cfg cfg, FusedA
                              : 0.0;
   PairInfo R;
   R.have = false; R.off = 2; R.prob = 0; R.j = R.k = 0;
-  if (d < (cfg.n_sd + 1) / 2) R = pair_prob_body<KERNEL, BREAKUP>(cfg, A, d, W, u_b);
+  // (the last step of a call whose steps carried tags walks tagged words: it takes the ids out of
+  // them and ignores the tags)
+  constexpr bool TAGS = PAIR_ALL_TAGS(KERNEL, BREAKUP, CLOSED);
+  if (d < (cfg.n_sd + 1) / 2) R = pair_prob_body<KERNEL, BREAKUP, TAGS>(cfg, A, d, W, u_b);
   double p = R.prob;
   if (p != 0) p /= (double)cfg.substeps;  // collision.py:279
   pair_update_body<BREAKUP>(cfg, A, d, d < W / 2, p, u, u_b, true, R.off, R.j, R.k,
@@ -963,7 +1123,9 @@ template <int KERNEL>
 __global__ void __launch_bounds__(BIN_THREADS) PAIR_SORT_BUDGET(KERNEL)
 k_pair_all_sort(sdm_step_cfg cfg, FusedArgs A, SortAhead X) {
   VELOCITY_LAW_PROMISE(false);
+#define PAIR_BODY_TAGS (PAIR_TAGS && NARROW_IDX && KERNEL == SDM_KERNEL_GOLOVIN)
 #include "pair_all_sort_body.inc"
+#undef PAIR_BODY_TAGS
 }
 
 // the sibling for the closed-form laws.  It stays at one workgroup per CU: under the budget of
@@ -972,7 +1134,9 @@ k_pair_all_sort(sdm_step_cfg cfg, FusedArgs A, SortAhead X) {
 template <int KERNEL>
 __global__ void __launch_bounds__(BIN_THREADS)
 k_pair_all_sort_closed(sdm_step_cfg cfg, FusedArgs A, SortAhead X) {
+#define PAIR_BODY_TAGS false
 #include "pair_all_sort_body.inc"
+#undef PAIR_BODY_TAGS
 }
 
 #ifdef PAIR_PROFILE
@@ -3387,6 +3551,7 @@ static int collision_step(sdm_ctx *ctx, const sdm_step_cfg *cfg, sdm_step_state 
                                    presorted ? &prologue : nullptr, narrow_in);
       if (rc) return rc;
       A.narrow = narrow_in ? 2 : 0;
+      if (PAIR_TAGS && narrow_in && ctx->presorted.tagged) A.narrow |= NARROW_TAG_IN;
       A.rec = views.rec;
       A.rec_fmt = views.fmt;
       A.ovf_head = views.ovf_head;
@@ -3452,6 +3617,11 @@ static int collision_step(sdm_ctx *ctx, const sdm_step_cfg *cfg, sdm_step_state 
         // (SDM_OPT_NARROW_STEP = 1: int64_t as at the ends of a call)
         const bool narrow_out = NARROW_IDX && !ctx->opt_wide_step && !sharded;
         if (narrow_out) A.narrow |= 1;
+        // ... with tags beside them where the call carries them (sdm_collision_run decides; the
+        // successor words hold 30 bits of a terminal word, the packed records only the id)
+        const bool tag_out = PAIR_TAGS && narrow_out && ctx->tags_call && !closed &&
+                             cfg->kernel == SDM_KERNEL_GOLOVIN && A.rec_fmt == SDM_REC_CHAIN;
+        if (tag_out) A.narrow |= NARROW_TAG_OUT;
         const dim3 grid((unsigned)(B.n_tiles + grid_for((N + 1) / 2, BIN_THREADS)));
 #ifdef PAIR_PROFILE
         pair_prof_launch[0] = grid.x; pair_prof_launch[1] = (long long)B.lds_bytes;
@@ -3474,6 +3644,7 @@ static int collision_step(sdm_ctx *ctx, const sdm_step_cfg *cfg, sdm_step_state 
 #undef PAIR_SORT
         ctx->presorted.active = true;
         ctx->presorted.narrow = narrow_out;
+        ctx->presorted.tagged = tag_out;
         ctx->presorted.owner = st;
       } else {
         DISPATCH_PAIR(k_pair_all, dim3(grid_for((N + 1) / 2)));
@@ -3665,6 +3836,7 @@ static int collision_step(sdm_ctx *ctx, const sdm_step_cfg *cfg, sdm_step_state 
     ctx->carry.n_active_cells = n_active_cells;
   }
   if (A.slots && fold_counters) {
+    if (PAIR_TAGS && ctx->tags_call) A.narrow |= NARROW_TAG_FOLD;
     hipLaunchKernelGGL(k_fold_counters, one, dim3(SDM_CNT_SLOTS), 0, s, A);
     LAUNCH_CHECK();
   }
@@ -3714,6 +3886,7 @@ extern "C" int sdm_collision_step(sdm_ctx *ctx, const sdm_step_cfg *cfg, sdm_ste
   ctx->carry.active = false;
   ctx->lists.active = false;
   ctx->presorted.active = false;
+  ctx->tags_call = false;
   ctx->resort_backoff = 0;
   return collision_step(ctx, cfg, st, res, flags, true, false);
 }
@@ -3969,6 +4142,28 @@ extern "C" int sdm_collision_run(sdm_ctx *ctx, const sdm_step_cfg *cfg, sdm_step
   ctx->lists.active = false;
   ctx->presorted.active = false;
   ctx->resort_backoff = 0;
+  // tags beside the 32-bit ids between the steps of this call (pair_tag.h).  What is decided here
+  // holds for every step; that a step rides the next one's sort, writes narrow ids and builds
+  // successor words is its own to find out (collision_step: tag_out).  The conditions on the
+  // numbers are those under which the probability is monotone in multiplicity and mass
+  ctx->tags_call = PAIR_TAGS && NARROW_IDX && cfg && st && n_steps >= 2 && !ctx->opt_no_pair_tags &&
+                   !ctx->opt_wide_step && !ctx->opt_no_presort && !ctx->opt_records &&
+                   cfg->n_cell == 1 && !cfg->adaptive && !cfg->enable_breakup &&
+                   cfg->kernel == SDM_KERNEL_GOLOVIN && !cfg->optimized_random &&
+                   cfg->n_sd >= 2 && cfg->n_sd <= (int64_t)PAIR_TAG_ID_MASK &&
+                   cfg->mass_attr >= 0 && cfg->mass_attr < cfg->n_attr &&
+                   cfg->kernel_param[0] >= 0 && cfg->rho_w > 0 && cfg->dt >= 0 && cfg->dv > 0 &&
+                   !st->cell_owned && st->multiplicity && st->attributes && ctx->cnt_slots &&
+                   !ctx->graph_capture;
+  if (ctx->tags_call) {
+    // the call's references: one pass over the two columns, on the stream, no read-back
+    int64_t blocks = (int64_t)grid_for(cfg->n_sd);
+    if (blocks > 1024) blocks = 1024;
+    hipLaunchKernelGGL(k_tag_ref, dim3((unsigned)blocks), dim3(SDM_BLOCK), 0, ctx->stream,
+                       st->multiplicity, st->attributes + (int64_t)cfg->mass_attr * cfg->n_sd,
+                       cfg->n_sd, ctx->cnt_slots);
+    LAUNCH_CHECK();
+  }
   sdm_step_result total;
   memset(&total, 0, sizeof(total));
   total.valid_n_sd = -1;
@@ -4047,6 +4242,7 @@ extern "C" int sdm_collision_run(sdm_ctx *ctx, const sdm_step_cfg *cfg, sdm_step
     total.rng_offset_breakup = one.rng_offset_breakup;
   }
   if (!pairs_known) total.n_pairs = -1;
+  ctx->tags_call = false;
   *res = total;
   return SDM_OK;
 }

@@ -25,6 +25,12 @@
   WalkSeg L;
   L.seg = nullptr; L.seg_first = L.seg_len = L.n0 = L.n1 = 0;
   const int64_t my_tile = 2 * (int64_t)lb * BIN_THREADS / EV_TILE;
+  // {both counts of a tagged step, waves that have added theirs} (the end of this text), zero
+  // before the first barrier
+  __shared__ unsigned tag_cnt[2];
+  const bool tag_count = PAIR_BODY_TAGS && PAIR_TAG_COUNT && (A.narrow & NARROW_TAG_OUT) &&
+                         (A.narrow & NARROW_TAG_IN);  // uniform
+  if (tag_count && threadIdx.x < 2) tag_cnt[threadIdx.x] = 0;
 #ifdef WALK_NO_SEG  // (tuning builds: every look-up from the tables)
   if (false) {
 #else
@@ -40,14 +46,63 @@
     L.seg_len = EV_TILE;
     L.n0 = w.x;
     L.n1 = w.y;
+  } else if (tag_count) {
+    __syncthreads();
   }
   if (d == 0) A.ctl[CTL_PAIRS] += W / 2;
   const double u = draw_at(A.s_rand, A.rng_inc, A.rng_aff, d);
   PairInfo R;
   R.have = false; R.off = 2; R.prob = 0; R.j = R.k = 0;
-  if (d < (cfg.n_sd + 1) / 2) R = pair_prob_body<KERNEL, false>(cfg, A, d, W, 0.0, &L);
+  // PAIR_BODY_TAGS (set by the including kernel; true in k_pair_all_sort<Golovin> alone): tags
+  // beside the ids (pair_tag.h).  Everywhere else the lines below are what they were
+  constexpr bool TAGGED = PAIR_BODY_TAGS;
+  PairTags T;
+  T.u = u; T.tj = T.tk = 0; T.skipped = false; T.mj = T.mk = 0.0;
+  if (d < (cfg.n_sd + 1) / 2)
+    R = pair_prob_body<KERNEL, false, TAGGED>(cfg, A, d, W, 0.0, &L, TAGGED ? &T : nullptr);
   double p = R.prob;
   if (p != 0) p /= (double)cfg.substeps;  // collision.py:279
-  pair_update_body<false>(cfg, A, d, d < W / 2, p, u, 0.0, true, R.off, R.j, R.k, 2 * d + R.off,
-                          true);
+  const bool tag_out = TAGGED && (A.narrow & NARROW_TAG_OUT);
+  const int died = pair_update_body<false>(cfg, A, d, d < W / 2, p, u, 0.0, true, R.off, R.j, R.k,
+                                           2 * d + R.off, !tag_out);
+  if (tag_out) {
+    if (R.have) {
+      // the slot's two words (i = 2d on this route): a skipped pair keeps the tags it came with,
+      // a gathered one gets those of its state as the update left it; a dead member the bare flag
+      uint32_t tj = T.tj, tk = T.tk;
+      if (!T.skipped) {
+        int64_t nj = R.nj, nk = R.nk;
+        double mj = T.mj, mk = T.mk;
+        if (ceil(p - u) != 0) {  // collided: this thread's own writes, read back
+          const SD sj = sd_load(cfg, A, R.j, false), sk = sd_load(cfg, A, R.k, false);
+          nj = sj.n; mj = sj.m;
+          nk = sk.n; mk = sk.m;
+        }
+        const int64_t n_ref = A.slots[TAG_N_REF];
+        const double m_base = pair_tag_m_base(A.slots[TAG_M_MAX]);
+        tj = pair_tag_encode(nj, mj, n_ref, m_base);
+        tk = pair_tag_encode(nk, mk, n_ref, m_base);
+      }
+      const uint32_t wj = (died & 1) ? (uint32_t)cfg.n_sd : (uint32_t)R.j | (tj << PAIR_TAG_SHIFT);
+      const uint32_t wk = (died & 2) ? (uint32_t)cfg.n_sd : (uint32_t)R.k | (tk << PAIR_TAG_SHIFT);
+      *(int2 *)((int32_t *)A.idx + 2 * d) = make_int2((int32_t)wj, (int32_t)wk);
+    }
+    if (tag_count) {
+      // a tagged step's pairs by what became of them: one add per count and workgroup, made by
+      // the wave that arrives last - no barrier, a wave that is done leaves.  Both counts in one
+      // LDS word, at most BIN_THREADS = 2^10 each.  (The counting costs 0.5 us of the step with or
+      // without a barrier here: profiles/README.md, round 10; -DPAIR_TAG_COUNT=0 leaves it out)
+      const unsigned skipped = __popcll(__ballot(R.have && T.skipped));
+      const unsigned gathered = __popcll(__ballot(R.have && !T.skipped));
+      if (lane_id() == 0) {
+        atomicAdd(&tag_cnt[0], skipped | (gathered << 16));
+        if (atomicAdd(&tag_cnt[1], 1u) == BIN_THREADS / SDM_WAVE - 1) {
+          const unsigned both = atomicAdd(&tag_cnt[0], 0u);  // (after every wave's add: LDS keeps a wave's order)
+          int64_t *slot = &A.slots[(blockIdx.x & (SDM_CNT_SLOTS - 1)) * SDM_CNT_STRIDE + SLOT_TAG_SKIPPED];
+          if (both & 0xffffu) atomicAdd((unsigned long long *)&slot[0], (unsigned long long)(both & 0xffffu));
+          if (both >> 16) atomicAdd((unsigned long long *)&slot[1], (unsigned long long)(both >> 16));
+        }
+      }
+    }
+  }
   PAIR_PROF_EXIT(1);
