@@ -45,6 +45,8 @@ PARCEL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "sdm_parcel
 PARCEL_DIAG_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "sdm_parcel_diag.h")
 # and the parcel with aqueous chemistry (cloud processing of aerosol)
 PARCEL_CHEM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "sdm_parcel_chem.h")
+# and the ventilated parcel (Reynolds numbers inside the step loop)
+PARCEL_VENT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "sdm_parcel_vent.h")
 # SDM_HIP_LIB: another build of the same library (tuning variants); still no fallback
 HIP_LIB_PATH = os.environ.get("SDM_HIP_LIB") or os.path.join(_HERE, "libsdm_hip.so")
 
@@ -222,6 +224,15 @@ class ParcelDiag(ctypes.Structure):  # == sdm_parcel_diag
 class ParcelChemProfile(ctypes.Structure):  # == sdm_parcel_chem_profile (include/sdm_parcel_chem.h)
     _fields_ = [("mixing_ratio", c_ptr * 6), ("aq_total", c_ptr * 7), ("n_flagged", c_ptr),
                 ("dv", c_ptr)]
+
+
+class ParcelVent(ctypes.Structure):  # == sdm_parcel_vent (include/sdm_parcel_vent.h)
+    _fields_ = [
+        ("velocity_law", ctypes.c_int32), ("velocity_terms", ctypes.c_int32),
+        ("velocity_params", c_ptr), ("gk_a", c_ptr), ("gk_b", c_ptr), ("gk_table_len", c_i64),
+        ("gk_factor", c_f64), ("gk_top", c_f64), ("air_density", c_ptr),
+        ("air_dynamic_viscosity", c_ptr), ("reynolds_number", c_ptr), ("out_of_table", c_ptr),
+    ]
 
 
 class RelaxedVelocityCfg(ctypes.Structure):  # == sdm_relaxed_velocity_cfg
@@ -402,6 +413,7 @@ _initialisation_library = None
 _parcel_library = None
 _parcel_diag_library = None
 _parcel_chem_library = None
+_parcel_vent_library = None
 
 
 def hip_library():
@@ -509,6 +521,15 @@ def parcel_chem_library():
         _parcel_chem_library = Library(HIP_LIB_PATH, "the HIP kernels of pysdm_amd",
                                        header=PARCEL_CHEM_HEADER_PATH)
     return _parcel_chem_library
+
+
+def parcel_vent_library():
+    """libsdm_hip.so bound to include/sdm_parcel_vent.h (same file, same contexts)"""
+    global _parcel_vent_library  # pylint: disable=global-statement
+    if _parcel_vent_library is None:
+        _parcel_vent_library = Library(HIP_LIB_PATH, "the HIP kernels of pysdm_amd",
+                                       header=PARCEL_VENT_HEADER_PATH)
+    return _parcel_vent_library
 
 
 def pcg64_state_inc(seed):

@@ -192,14 +192,13 @@ __global__ void k_temperature_pressure_rh(const double *rhod, const double *thd,
 
 __global__ void k_air_density(double *out, const double *rhod, const double *qv, int64_t n) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (i < n) out[i] = rhod[i] * (1 + qv[i]);  // libcloudphplusplus.py:58
+  if (i < n) out[i] = air_density_of(rhod[i], qv[i]);
 }
 
 __global__ void k_air_dynamic_viscosity(double *out, const double *temperature, int64_t n, Kc k) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const double t = temperature[i];  // zografos_et_al_1987.py:17-23
-  out[i] = k.Z3 * sdm_pow(t, 3.0) + k.Z2 * sdm_pow(t, 2.0) + k.Z1 * t + k.Z0;
+  out[i] = air_dynamic_viscosity_of(temperature[i], k.Z3, k.Z2, k.Z1, k.Z0);
 }
 
 __global__ void k_critical_volume(double *v_cr, const double *kappa, const double *v_dry,
@@ -214,8 +213,8 @@ __global__ void k_reynolds_number(double *out, const int64_t *cell_id, const dou
                                   int64_t n) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const int64_t c = cell_id[i];  // liquid_spheres.py:29-31
-  out[i] = 2 * radius[i] * u[i] * rho[c] / eta[c];
+  const int64_t c = cell_id[i];
+  out[i] = reynolds_number_of(radius[i], u[i], rho[c], eta[c]);
 }
 
 __global__ void k_explicit_euler(double *y, int64_t n, double dt, double dy_dt) {

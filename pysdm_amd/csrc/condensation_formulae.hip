@@ -127,7 +127,13 @@ struct GeneralFormulae {
   // step_impl's cell scalars, cm.py:288-302,429-430
   DF static void cellwide(const CondArgs<GeneralFormulae> &g, int64_t cell, double rhod,
                           double thd, double qv, Cellwide &w) {
-    const cf_k *k = &g.k.f;
+    cellwide_of(&g.k.f, g.k.air_dynamic_viscosity + cell, g.k.air_density + cell, rhod, thd, qv,
+                w);
+  }
+  // ... with the cell's air behind two pointers, read only with a ventilation
+  DF static void cellwide_of(const cf_k *k, const double *air_dynamic_viscosity,
+                             const double *air_density, double rhod, double thd, double qv,
+                             Cellwide &w) {
     w.T = cf_svt_T(k, rhod, thd);
     const double p = cf_svt_p(k, rhod, w.T, qv);
     const double pv = cf_svt_pv(k, p, qv);
@@ -138,7 +144,7 @@ struct GeneralFormulae {
     w.RH = pv / w.pvs;
     w.Sc = 0.0;
     if (CF_O(VENTILATION) != SDM_COND_VENT_NEGLECT)
-      w.Sc = cf_air_schmidt_number(g.k.air_dynamic_viscosity[cell], w.DTp, g.k.air_density[cell]);
+      w.Sc = cf_air_schmidt_number(*air_dynamic_viscosity, w.DTp, *air_density);
     w.lambdaK = cf_lambdaK(k, w.T, p);
     w.lambdaD = cf_lambdaD(k, w.DTp, w.T);
   }
@@ -185,6 +191,28 @@ __global__ __launch_bounds__(COND_CB) void k_parcel_f_d(ParcelArgs<GeneralFormul
                                                         ParcelDiag d) {
   parcel_steps<GeneralFormulae, true>(a, &d);
 }
+// include/sdm_parcel_vent.h: the general formulae for a parcel whose air density and viscosity
+// change from step to step inside the kernel - the solver's cell scalars read the parcel's pair
+// from LDS (parcel_solver.h), everything else is GeneralFormulae's
+struct VentFormulae : GeneralFormulae {
+  DF static void cellwide(const CondArgs<VentFormulae> &g, int64_t, double rhod, double thd,
+                          double qv, Cellwide &w) {
+    const VentLds *vl = vent_lds();
+    cellwide_of(&g.k.f, &vl->air[PA_ETA], &vl->air[PA_RHO], rhod, thd, qv, w);
+  }
+  DF static double air_dynamic_viscosity(const Kg &k, double T) {  // the body of the stage kernel
+    return air_dynamic_viscosity_of(T, k.f.c[SDM_COND_K_ZOGRAFOS_T3], k.f.c[SDM_COND_K_ZOGRAFOS_T2],
+                                    k.f.c[SDM_COND_K_ZOGRAFOS_T1], k.f.c[SDM_COND_K_ZOGRAFOS_T0]);
+  }
+};
+__global__ __launch_bounds__(COND_CB) void k_parcel_v(ParcelArgs<VentFormulae> a, ParcelVent v) {
+  parcel_steps<VentFormulae, false, true>(a, nullptr, &v);
+}
+__global__ __launch_bounds__(COND_CB) void k_parcel_v_d(ParcelArgs<VentFormulae> a, ParcelDiag d,
+                                                        ParcelVent v) {
+  parcel_steps<VentFormulae, true, true>(a, &d, &v);
+}
+
 __global__ __launch_bounds__(COND_CB) void k_parcel_diagnose_f(
     ParcelDiagnoseArgs<GeneralFormulae> a) {
   parcel_diagnose_cells<GeneralFormulae>(a);
@@ -263,7 +291,7 @@ int sdm_parcel_launch_general(sdm_ctx *ctx, const ParcelCall &call,
   ParcelArgs<GeneralFormulae> a;
   SDM_PARCEL_FILL_ARGS(a, call);
   ARG_TRY(formulae && formulae_of(call.consts, formulae, &a.c.k.f));
-  // (ventilation needs a fall velocity per droplet per step: it stays on the stage route)
+  // (a ventilated parcel has kernels and an entry point of its own: sdm_parcel_launch_vent)
   ARG_TRY(formulae->option[SDM_COND_OPT_VENTILATION] == SDM_COND_VENT_NEGLECT);
   ARG_TRY(formulae->option[SDM_COND_OPT_SURFACE_TENSION] == SDM_COND_SGM_CONSTANT || call.f_org);
   a.c.k.f_org = call.f_org;
@@ -277,6 +305,42 @@ int sdm_parcel_launch_general(sdm_ctx *ctx, const ParcelCall &call,
   } else {
     hipLaunchKernelGGL(k_parcel_f, dim3((unsigned)call.n_parcel), dim3(COND_CB), 0, ctx->stream,
                        a);
+  }
+  LAUNCH_CHECK();
+  return SDM_OK;
+}
+
+int sdm_parcel_launch_vent(sdm_ctx *ctx, const ParcelCall &call,
+                           const sdm_cond_formulae *formulae, const sdm_parcel_vent *vent) {
+  ParcelArgs<VentFormulae> a;
+  SDM_PARCEL_FILL_ARGS(a, call);
+  ARG_TRY(formulae && vent && formulae_of(call.consts, formulae, &a.c.k.f));
+  ARG_TRY(formulae->option[SDM_COND_OPT_VENTILATION] != SDM_COND_VENT_NEGLECT);
+  ARG_TRY(formulae->option[SDM_COND_OPT_SURFACE_TENSION] == SDM_COND_SGM_CONSTANT || call.f_org);
+  a.c.k.f_org = call.f_org;
+  a.c.k.reynolds_number = vent->reynolds_number;  // (written by the kernel before it is read)
+  a.c.k.vdry = call.vdry;
+  a.c.k.air_density = a.c.k.air_dynamic_viscosity = nullptr;  // (the parcel's pair is in LDS)
+  ParcelVent v;
+  v.law = vent->velocity_law;
+  v.terms = vent->velocity_terms;
+  v.params = vent->velocity_params;
+  v.gk_a = vent->gk_a;
+  v.gk_b = vent->gk_b;
+  v.gk_len = vent->gk_table_len;
+  v.gk_factor = vent->gk_factor;
+  v.gk_top = vent->gk_top;
+  v.air_density = vent->air_density;
+  v.air_dynamic_viscosity = vent->air_dynamic_viscosity;
+  v.reynolds_number = vent->reynolds_number;
+  v.out_of_table = vent->out_of_table;
+  if (call.requests) {
+    const ParcelDiag d{call.requests, call.diag};
+    hipLaunchKernelGGL(k_parcel_v_d, dim3((unsigned)call.n_parcel), dim3(COND_CB), 0, ctx->stream,
+                       a, d, v);
+  } else {
+    hipLaunchKernelGGL(k_parcel_v, dim3((unsigned)call.n_parcel), dim3(COND_CB), 0, ctx->stream,
+                       a, v);
   }
   LAUNCH_CHECK();
   return SDM_OK;

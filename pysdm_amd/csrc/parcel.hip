@@ -5,6 +5,8 @@
 // condensation_formulae.hip (a descriptor); this file reaches both through their launchers.
 // Likewise include/sdm_parcel_diag.h: its request table is checked here and copied to device
 // memory once per call; k_parcel_d / k_parcel_f_d and k_parcel_diagnose(_f) read it there.
+// And include/sdm_parcel_vent.h: the same checks and chunking for formulae with a ventilation, on
+// k_parcel_v / k_parcel_v_d (condensation_formulae.hip).
 //
 // A call of n_steps enqueues ceil(n_steps / steps_per_launch) launches back to back on the
 // context's stream, without synchronising between them: one launch stays short on a shared card,
@@ -102,7 +104,8 @@ int sdm_parcel_prepare(sdm_ctx *ctx, const sdm_parcel_cfg *cfg, int64_t n_steps,
                        const double *w_mid, const sdm_parcel_profile *profile,
                        const double consts[34], const sdm_cond_formulae *formulae,
                        const sdm_parcel_requests *requests, const sdm_parcel_diag *diag,
-                       ParcelCall *out, bool *with_diag_out, bool *nothing_to_do) {
+                       ParcelCall *out, bool *with_diag_out, bool *nothing_to_do,
+                       bool ventilated) {
   *nothing_to_do = true;
   *with_diag_out = false;
   ARG_TRY(ctx && cfg && consts && state);
@@ -110,7 +113,9 @@ int sdm_parcel_prepare(sdm_ctx *ctx, const sdm_parcel_cfg *cfg, int64_t n_steps,
   ARG_TRY(cfg->multiplier >= 1 && cfg->fuse >= 0 && cfg->max_iters >= 0 && cfg->dt > 0);
   ARG_TRY(cfg->dt_min != 0);
   ARG_TRY(cfg->steps_per_launch >= 0);
-  if (formulae)  // (the general launcher checks the rest of the descriptor)
+  if (ventilated)  // (the launchers check the rest of the descriptor)
+    ARG_TRY(formulae && formulae->option[SDM_COND_OPT_VENTILATION] != SDM_COND_VENT_NEGLECT);
+  else if (formulae)
     ARG_TRY(formulae->option[SDM_COND_OPT_VENTILATION] == SDM_COND_VENT_NEGLECT);
   const bool with_diag = wants_output(diag);  // otherwise: the kernels of sdm_parcel_run
   if (requests) {
@@ -183,6 +188,45 @@ extern "C" int sdm_parcel_run_diag(sdm_ctx *ctx, const sdm_parcel_cfg *cfg, int6
     call.k_count = n_steps - k0 < per_launch ? n_steps - k0 : per_launch;
     const int launched = formulae ? sdm_parcel_launch_general(ctx, call, formulae)
                                   : sdm_parcel_launch_default(ctx, call);
+    if (launched != SDM_OK) return launched;
+  }
+  return SDM_OK;
+}
+
+// include/sdm_parcel_vent.h: the same chunking on the ventilated kernels
+extern "C" int sdm_parcel_run_vent(sdm_ctx *ctx, const sdm_parcel_cfg *cfg, int64_t n_steps,
+                                   int64_t n_parcel, int64_t n_sd, const int64_t *parcel_start,
+                                   double *water_mass, const int64_t *multiplicity,
+                                   const double *vdry, const double *kappa, const double *f_org,
+                                   double *v_cr, const sdm_parcel_state *state,
+                                   const double *w_mid, const sdm_parcel_profile *profile,
+                                   const double consts[34], const sdm_cond_formulae *formulae,
+                                   const sdm_parcel_requests *requests,
+                                   const sdm_parcel_diag *diag, const sdm_parcel_vent *vent) {
+  ARG_TRY(formulae && vent);
+  ARG_TRY(formulae->option[SDM_COND_OPT_VENTILATION] != SDM_COND_VENT_NEGLECT);
+  const int law = vent->velocity_law;
+  ARG_TRY(law >= SDM_VELOCITY_LAW_GUNN_KINZER && law <= SDM_VELOCITY_LAW_POWER_SERIES);
+  if (law == SDM_VELOCITY_LAW_GUNN_KINZER)
+    ARG_TRY(vent->gk_a && vent->gk_b && vent->gk_table_len >= 1);
+  if (law == SDM_VELOCITY_LAW_ROGERS_YAU) ARG_TRY(vent->velocity_params);
+  if (law == SDM_VELOCITY_LAW_POWER_SERIES)
+    ARG_TRY(vent->velocity_terms >= 0 && vent->velocity_terms <= SDM_VELOCITY_MAX_TERMS &&
+            (vent->velocity_terms == 0 || vent->velocity_params));
+  ARG_TRY(vent->air_density && vent->air_dynamic_viscosity && vent->reynolds_number);
+  ParcelCall call;
+  bool with_diag, nothing_to_do;
+  const int prepared = sdm_parcel_prepare(ctx, cfg, n_steps, n_parcel, n_sd, parcel_start,
+                                          water_mass, multiplicity, vdry, kappa, f_org, v_cr, state,
+                                          w_mid, profile, consts, formulae, requests, diag, &call,
+                                          &with_diag, &nothing_to_do, true);
+  if (prepared != SDM_OK || nothing_to_do) return prepared;
+  const int64_t per_launch =
+      cfg->steps_per_launch > 0 ? cfg->steps_per_launch : SDM_PARCEL_STEPS_PER_LAUNCH;
+  for (int64_t k0 = 0; k0 < n_steps; k0 += per_launch) {
+    call.k0 = k0;
+    call.k_count = n_steps - k0 < per_launch ? n_steps - k0 : per_launch;
+    const int launched = sdm_parcel_launch_vent(ctx, call, formulae, vent);
     if (launched != SDM_OK) return launched;
   }
   return SDM_OK;

@@ -44,7 +44,7 @@
 #define SDM_PARCEL_SOLVER_H
 #include "condensation_solver.h"
 #include "physics.h"
-#include "../../include/sdm_parcel_diag.h"
+#include "../../include/sdm_parcel_vent.h"
 
 // one sdm_parcel_run call as the launchers take it (host struct; pointers are device pointers)
 struct ParcelCall {
@@ -73,7 +73,8 @@ struct ParcelDiagnoseCall {
 // parcel.hip: the checks of sdm_parcel_run_diag and the ParcelCall of its arguments (k0 / k_count
 // left to the caller); *with_diag: the request table is in device memory and `diag` has outputs.
 // It synchronises the stream once (parcel_start is read back).  n_parcel or n_steps 0: SDM_OK with
-// *nothing_to_do set
+// *nothing_to_do set.  `ventilated`: the caller is sdm_parcel_run_vent, the only entry that takes
+// (and then demands) a ventilation other than Neglect
 int sdm_parcel_prepare(sdm_ctx *ctx, const sdm_parcel_cfg *cfg, int64_t n_steps, int64_t n_parcel,
                        int64_t n_sd, const int64_t *parcel_start, double *water_mass,
                        const int64_t *multiplicity, const double *vdry, const double *kappa,
@@ -81,11 +82,16 @@ int sdm_parcel_prepare(sdm_ctx *ctx, const sdm_parcel_cfg *cfg, int64_t n_steps,
                        const double *w_mid, const sdm_parcel_profile *profile,
                        const double consts[34], const sdm_cond_formulae *formulae,
                        const sdm_parcel_requests *requests, const sdm_parcel_diag *diag,
-                       ParcelCall *call, bool *with_diag, bool *nothing_to_do);
+                       ParcelCall *call, bool *with_diag, bool *nothing_to_do,
+                       bool ventilated = false);
 // condensation.hip / condensation_formulae.hip: one launch of the default / general kernel
 int sdm_parcel_launch_default(sdm_ctx *ctx, const ParcelCall &call);
 int sdm_parcel_launch_general(sdm_ctx *ctx, const ParcelCall &call,
                               const sdm_cond_formulae *formulae);
+// condensation_formulae.hip: one launch of the ventilated kernel (include/sdm_parcel_vent.h;
+// `vent` was checked by the caller)
+int sdm_parcel_launch_vent(sdm_ctx *ctx, const ParcelCall &call,
+                           const sdm_cond_formulae *formulae, const sdm_parcel_vent *vent);
 int sdm_parcel_diagnose_default(sdm_ctx *ctx, const ParcelDiagnoseCall &call);
 int sdm_parcel_diagnose_general(sdm_ctx *ctx, const ParcelDiagnoseCall &call,
                                 const sdm_cond_formulae *formulae);
@@ -266,12 +272,49 @@ DF void parcel_diagnose_cells(const ParcelDiagnoseArgs<P> &a) {
 // the slots of the parcel's scalars in LDS
 enum { PS_Z, PS_RHOD, PS_THD, PS_QV, PS_T, PS_P, PS_RH, PS_QV_PREV, PS_PRHOD, PS_PZ, PS_N };
 
-template <class P, bool DIAG = false>
-DF void parcel_steps(const ParcelArgs<P> &a, const ParcelDiag *d = nullptr) {
+// ---- ventilation (include/sdm_parcel_vent.h) -------------------------------------------------
+// parcel_steps<P, DIAG, true> (k_parcel_v, k_parcel_v_d) forms every row's Reynolds number in the
+// pass that forms its critical volume: radius, fall velocity and Re by the device functions the
+// stage kernels run (physics.h), written to the `reynolds_number` column the solver's policy reads
+// back - row q by lane q % COND_CB on both sides, so program order is all the ordering.  The
+// parcel's air density and viscosity live in LDS beside s_par: the pair the step reads, and the
+// pair lane 0 forms after the advance, which replaces the first only when the step has succeeded.
+// The policy's cellwide() finds the first pair through vent_lds() (a function-scope __shared__
+// object is one object however often the function is inlined).
+struct ParcelVent {  // == sdm_parcel_vent
+  int32_t law, terms;
+  const double *params, *gk_a, *gk_b;
+  int64_t gk_len;
+  double gk_factor, gk_top;
+  double *air_density, *air_dynamic_viscosity, *reynolds_number;
+  int64_t *out_of_table;
+};
+enum { PA_RHO, PA_ETA, PA_NEW_RHO, PA_NEW_ETA, PA_N };
+struct VentLds {
+  double air[PA_N];
+  int out_of_range;
+};
+DF VentLds *vent_lds() {
+  __shared__ VentLds s_vent;
+  return &s_vent;
+}
+// the law is uniform over the launch; each branch is the device function of its stage kernel
+DF double vent_velocity(const ParcelVent &v, double r) {
+  if (v.law == SDM_VELOCITY_LAW_GUNN_KINZER)
+    return gk_interpolate(r, v.gk_factor, v.gk_a, v.gk_b, v.gk_len);
+  if (v.law == SDM_VELOCITY_LAW_ROGERS_YAU) return rogers_yau_velocity(r, v.params);
+  return power_series_velocity(r, v.terms, v.params, v.params + v.terms);
+}
+
+template <class P, bool DIAG = false, bool VENT = false>
+DF void parcel_steps(const ParcelArgs<P> &a, const ParcelDiag *d = nullptr,
+                     const ParcelVent *v = nullptr) {
   __shared__ double s_par[PS_N];
   __shared__ int64_t s_nsub;
   DiagLds dl;
   if constexpr (DIAG) attach_diag_lds(dl);
+  [[maybe_unused]] VentLds *vl = nullptr;
+  if constexpr (VENT) vl = vent_lds();
   const CondArgs<P> &g = a.c;
   const typename P::K &k = g.k;
   const int tid = (int)threadIdx.x;
@@ -292,14 +335,25 @@ DF void parcel_steps(const ParcelArgs<P> &a, const ParcelDiag *d = nullptr) {
       s_par[PS_RH] = a.st.RH[c];
       s_par[PS_QV_PREV] = a.st.qv_prev[c];
       s_nsub = a.st.n_substeps[c];
+      if constexpr (VENT) {
+        vl->air[PA_RHO] = v->air_density[c];
+        vl->air[PA_ETA] = v->air_dynamic_viscosity[c];
+        vl->out_of_range = 0;
+      }
     }
     const double mass_of_dry_air = a.st.mass_of_dry_air[c];
     int64_t done = a.st.steps_done[c];
     int64_t failed = -1;
+    [[maybe_unused]] bool out_of_table = false;
     for (int64_t j = 0; j < a.k_count; ++j) {
       __syncthreads();  // lane 0's state of the previous step (or the load above) is in LDS
       const double thd = s_par[PS_THD], qv = s_par[PS_QV], rhod = s_par[PS_RHOD];
       const double T = s_par[PS_T];
+      [[maybe_unused]] double air_rho = 0, air_eta = 0;  // the pair this step's Re reads
+      if constexpr (VENT) {
+        air_rho = vl->air[PA_RHO];
+        air_eta = vl->air[PA_ETA];
+      }
       double prhod, dv;
       {  // advance_parcel_vars, parcel.py:101-134 (hydrostatics.drho_dz inlined)
         const double p = s_par[PS_P];
@@ -320,6 +374,31 @@ DF void parcel_steps(const ParcelArgs<P> &a, const ParcelDiag *d = nullptr) {
           s_par[PS_PRHOD] = prhod;
         }
       }
+      if constexpr (VENT) {
+        // Moist.sync of this step (moist.py:73-100): the pair the NEXT step reads, from the
+        // advanced rhod and the thd and qv of before this step's condensation
+        if (tid == 0) {
+          double sync_T, sync_p, sync_RH;
+          P::tprh(k, prhod, thd, qv, sync_T, sync_p, sync_RH);
+          vl->air[PA_NEW_RHO] = air_density_of(prhod, qv);
+          vl->air[PA_NEW_ETA] = P::air_dynamic_viscosity(k, sync_T);
+        }
+        // the table's range, before anything of the step is written
+        if (v->law == SDM_VELOCITY_LAW_GUNN_KINZER) {  // (uniform)
+          const double inv_pi_4_3 = 1 / P::pi_4_3(k);
+          bool over = false;
+          for (int64_t q = tid; q < n; q += COND_CB)
+            over = over || radius_of_volume(volume_of_mass(g.water_mass[row0 + q], P::rho_w(k)),
+                                            inv_pi_4_3) > v->gk_top;
+          if (over) vl->out_of_range = 1;
+          __syncthreads();
+          if (vl->out_of_range) {  // uniform; lane 0 clears the flag when it loads the next parcel
+            failed = done;
+            out_of_table = true;
+            break;
+          }
+        }
+      }
       // the critical volume of every row at the parcel's temperature; the copy of the masses the
       // solver writes in place
       for (int64_t q = tid; q < n; q += COND_CB) {
@@ -327,6 +406,10 @@ DF void parcel_steps(const ParcelArgs<P> &a, const ParcelDiag *d = nullptr) {
         const double m = g.water_mass[row];
         a.v_cr[row] = P::critical_volume(k, row, g.kappa[row], g.vdry[row], m / P::rho_w(k), T);
         if (q >= COND_CH) a.mass_backup[row] = m;
+        if constexpr (VENT) {  // attributes/physics/reynolds_number.py of the mass before the step
+          const double r = radius_of_volume(volume_of_mass(m, P::rho_w(k)), 1 / P::pi_4_3(k));
+          v->reynolds_number[row] = reynolds_number_of(r, vent_velocity(*v, r), air_rho, air_eta);
+        }
       }
       cs.init();
       const SolveOut s = solve_cell<P>(cs, g, thd, qv, rhod, prhod, thd, qv, dv, s_nsub);
@@ -356,6 +439,10 @@ DF void parcel_steps(const ParcelArgs<P> &a, const ParcelDiag *d = nullptr) {
         s_par[PS_P] = np;
         s_par[PS_RH] = nRH;
         s_nsub = ns;
+        if constexpr (VENT) {  // (every lane's reads of the old pair ended before the solver's
+          vl->air[PA_RHO] = vl->air[PA_NEW_RHO];  // last barrier)
+          vl->air[PA_ETA] = vl->air[PA_NEW_ETA];
+        }
         // the counters and RH_max are not read by the next step: straight to the state arrays
         a.st.n_activating[c] = s.o.n_activating;
         a.st.n_deactivating[c] = s.o.n_deactivating;
@@ -398,6 +485,11 @@ DF void parcel_steps(const ParcelArgs<P> &a, const ParcelDiag *d = nullptr) {
       a.st.qv_prev[c] = s_par[PS_QV_PREV];
       a.st.n_substeps[c] = s_nsub;
       a.st.steps_done[c] = done;
+      if constexpr (VENT) {  // (a failed step left the pair as it was)
+        v->air_density[c] = vl->air[PA_RHO];
+        v->air_dynamic_viscosity[c] = vl->air[PA_ETA];
+        if (out_of_table && v->out_of_table) v->out_of_table[c] = 1;
+      }
     }
   }
 }

@@ -55,6 +55,21 @@ __device__ __forceinline__ double power_series_velocity(double r, int num_terms,
   return v;
 }
 
+// physics_methods.py:131-194, one element each: the bodies of k_air_density,
+// k_air_dynamic_viscosity (z = Zografos et al. 1987's T^3 .. T^0 coefficients) and
+// k_reynolds_number, which the ventilated parcel kernels evaluate inside their step loop
+__device__ __forceinline__ double air_density_of(double rhod, double qv) {
+  return rhod * (1 + qv);  // libcloudphplusplus.py:58
+}
+__device__ __forceinline__ double air_dynamic_viscosity_of(double t, double z3, double z2,
+                                                           double z1, double z0) {
+  return z3 * sdm_pow(t, 3.0) + z2 * sdm_pow(t, 2.0) + z1 * t + z0;  // zografos_et_al_1987.py:17-23
+}
+__device__ __forceinline__ double reynolds_number_of(double radius, double u, double rho,
+                                                     double eta) {
+  return 2 * radius * u * rho / eta;  // liquid_spheres.py:29-31
+}
+
 // collisions_methods.py:743-769, one pair
 __device__ __forceinline__ double linear_collection_efficiency(const double *__restrict__ P,
                                                                double ra, double rb,

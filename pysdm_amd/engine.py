@@ -43,6 +43,8 @@ class Engine:
     parcel_diag_library = None
     # likewise include/sdm_parcel_chem.h
     parcel_chem_library = None
+    # likewise include/sdm_parcel_vent.h
+    parcel_vent_library = None
     # whether the fused collision step of `library` can take the fall velocity from the
     # "relative fall momentum" row; an engine that cannot must refuse, not ignore the request
     fused_momentum_velocity = False
@@ -168,6 +170,14 @@ class Engine:
         self._before_call()
         self.parcel_chem_library.invoke(symbol, self.handle, args)
 
+    def call_parcel_vent(self, symbol, *args):
+        """a symbol of include/sdm_parcel_vent.h"""
+        if self.parcel_vent_library is None:
+            raise NotImplementedError(
+                f"engine `{self.name}` has no library for the ventilated parcel")
+        self._before_call()
+        self.parcel_vent_library.invoke(symbol, self.handle, args)
+
     def _before_call(self):
         pass
 
@@ -207,6 +217,7 @@ class HipEngine(Engine):
         self.parcel_library = abi.parcel_library()
         self.parcel_diag_library = abi.parcel_diag_library()
         self.parcel_chem_library = abi.parcel_chem_library()
+        self.parcel_vent_library = abi.parcel_vent_library()
         self.handle = abi.c_ptr()
         self.library.check(self.library.cdll.sdm_ctx_create(ctypes.byref(self.handle),
                                                             abi.c_int(device_index)))

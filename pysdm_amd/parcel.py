@@ -11,7 +11,15 @@ the critical volume) as engine arrays and runs time steps on one of two routes:
   (and its `_f` forms): the advance of the parcel's variables in Python floats, then
   `sdm_critical_volume`, `sdm_condensation` and `sdm_temperature_pressure_rh`, per parcel on
   slices of the columns with n_cell = 1.  It is the yardstick of the fused route (the two agree
-  bit for bit) and the only route with a ventilation other than Neglect.
+  bit for bit).
+
+With a ventilation other than Neglect and ``terminal_velocity=`` (a name or a law object of
+pysdm_amd.terminal_velocity) every droplet's Reynolds number is formed inside the step
+(include/sdm_parcel_vent.h, where the step and the timing of the air density and viscosity it reads
+are written out): the fused route calls `sdm_parcel_run_vent`, the stage route adds
+`sdm_air_density`, `sdm_air_dynamic_viscosity`, the radius, the law's `evaluate` and
+`sdm_reynolds_number`.  The parcels then carry `air_density`, `air_dynamic_viscosity` (state) and
+the `reynolds_number` column.
 
 The time step is the one include/sdm_parcel.h writes out (environments/parcel.py:101-153,
 environments/impl/moist.py:73-100, dynamics/condensation.py:95-131), with the hydrostatics
@@ -21,10 +29,13 @@ products of the state after every step: the fused route evaluates their request 
 kernel's step loop (`sdm_parcel_run_diag`, include/sdm_parcel_diag.h), the stage route with
 `sdm_parcel_diagnose` after each step; `diagnose` gives the products of the current state.
 """
+import ctypes
+
 import numpy as np
 
 from . import abi
 from . import chemistry as chem
+from . import terminal_velocity as tv
 from .condensation import (CONSTANT_NAMES, OPTION_ORDER, _option_name, check_formulae,
                            condensation_call, critical_volume_call, is_default,
                            temperature_pressure_rh_call)
@@ -38,6 +49,8 @@ _INT_FIELDS = ("n_substeps", "n_activating", "n_deactivating", "n_ripening", "st
                "failed_step")
 _LV = OPTION_ORDER.index("latent_heat_vapourisation")
 _SGM = OPTION_ORDER.index("surface_tension")
+_VENT = OPTION_ORDER.index("ventilation")
+VENT_STATE = ("air_density", "air_dynamic_viscosity")  # what a ventilated parcel carries
 CHEM_COUNTERS = ("n_failed", "n_negative", "n_exceeded")
 _DIAG_LANES = 256  # the partials of the SUM of include/sdm_parcel_diag.h
 
@@ -84,7 +97,7 @@ def parcel_cfg(formulae, setup, dt, steps_per_launch=0):
 
 def parcel_call(engine, formulae, cfg, *, n_steps, parcel_start, water_mass, multiplicity,
                 dry_volume, kappa, f_org, critical_volume, state, w_mid, profile=None,
-                descriptor=None, general=False, requests=None, diag=None, chem=None):
+                descriptor=None, general=False, requests=None, diag=None, chem=None, vent=None):
     """one `sdm_parcel_run` call with raw engine arrays: `state` / `profile` are dicts of engine
     arrays by the member names of sdm_parcel_state / sdm_parcel_profile (`profile` may be None or
     lack members), `w_mid` an engine array of n_steps x n_parcel.  PySDM's default formulae go to
@@ -95,9 +108,16 @@ def parcel_call(engine, formulae, cfg, *, n_steps, parcel_start, water_mass, mul
     `kappa_times_dry_volume`, `moles` (7 columns), `pH`, `do_chemistry_flag`, `mixing_ratios` (6
     arrays of n_parcel), `consts` (62), `dry_factor`, `counters` (3 arrays of n_parcel or None)
     and `profile` (None, or a dict with `mixing_ratio`: 6 arrays, `aq_total`: 7 arrays,
-    `n_flagged`, `dv`, each of n_steps x n_parcel; entries may be missing)"""
+    `n_flagged`, `dv`, each of n_steps x n_parcel; entries may be missing).  With `vent` the call
+    is `sdm_parcel_run_vent` (include/sdm_parcel_vent.h; with or without `requests`): a dict by
+    the member names of sdm_parcel_vent - the law's part as `vent_law` builds it, and the engine
+    arrays `air_density`, `air_dynamic_viscosity` (n_parcel each), `reynolds_number` (n_sd) and
+    optionally `out_of_table` (n_parcel, int64); `descriptor` may then be one of
+    `condensation.descriptor_of` naming a ventilation a `Formulae` refuses"""
     if descriptor is None:
         descriptor = check_formulae(formulae)
+    if vent is not None and chem is not None:
+        raise NotImplementedError("parcel: chemistry with ventilation is not served")
     n_parcel = engine.size(parcel_start) - 1
     if engine.size(w_mid) != n_steps * n_parcel:
         raise ValueError("parcel: w_mid must hold n_steps x n_parcel values")
@@ -120,7 +140,7 @@ def parcel_call(engine, formulae, cfg, *, n_steps, parcel_start, water_mass, mul
             parcel_start, water_mass, multiplicity, dry_volume, kappa, f_org, critical_volume,
             c_state, w_mid, c_profile, consts,
             None if is_default(descriptor) and not general else descriptor)
-    if requests is None and chem is None:
+    if requests is None and chem is None and vent is None:
         engine.call_parcel("sdm_parcel_run", *args)
         return
     c_diag = None
@@ -128,6 +148,11 @@ def parcel_call(engine, formulae, cfg, *, n_steps, parcel_start, water_mass, mul
         sizes = {"moment_0": requests.n_moments, "moments": requests.n_moments,
                  "spectrum": requests.n_bins, "dv": 1}
         c_diag = _diag_struct(engine, diag, sizes, n_steps * n_parcel)
+    if vent is not None:
+        engine.call_parcel_vent(
+            "sdm_parcel_run_vent", *args[:-1], descriptor, requests, c_diag,
+            _vent_struct(engine, vent, n_parcel, int(engine.size(water_mass))))
+        return
     if chem is None:
         engine.call_parcel_diag("sdm_parcel_run_diag", *args, requests, c_diag)
         return
@@ -137,6 +162,52 @@ def parcel_call(engine, formulae, cfg, *, n_steps, parcel_start, water_mass, mul
         chem["mixing_ratios"], chem["consts"], float(chem["dry_factor"]),
         *(chem.get("counters") or (None, None, None)),
         _chem_profile_struct(engine, chem.get("profile"), n_steps * n_parcel))
+
+
+def vent_law(engine, law):
+    """the law's members of sdm_parcel_vent for a law object of pysdm_amd.terminal_velocity: a dict
+    of scalars and engine arrays (to be kept alive by the caller for as long as calls use them)"""
+    name = tv.law_name(law)
+    out = {"velocity_law": abi.VELOCITY_LAWS[name], "velocity_terms": 0, "velocity_params": None,
+           "gk_a": None, "gk_b": None, "gk_table_len": 0, "gk_factor": 0.0, "gk_top": 0.0}
+    if name == "GunnKinzer1949":
+        out.update(gk_a=law.a, gk_b=law.b, gk_table_len=int(law.length),
+                   gk_factor=float(law.factor), gk_top=float(law.maximum_radius))
+    elif name == "RogersYau":
+        out["velocity_params"] = engine.upload(np.array(law.consts, dtype=float))
+    else:
+        if len(law.powers) > abi.VELOCITY_MAX_TERMS:
+            raise ValueError(f"a power series of more than {abi.VELOCITY_MAX_TERMS} terms")
+        out["velocity_terms"] = len(law.powers)
+        out["velocity_params"] = engine.upload(np.concatenate(
+            [np.asarray(law.prefactors, dtype=float), np.asarray(law.powers, dtype=float)]))
+    return out
+
+
+def _vent_struct(engine, vent, n_parcel, n_sd):
+    """abi.ParcelVent of a dict by the member names of sdm_parcel_vent"""
+    out = abi.ParcelVent()
+    law = vent["velocity_law"]
+    out.velocity_law = abi.VELOCITY_LAWS[law] if isinstance(law, str) else int(law)
+    out.velocity_terms = int(vent.get("velocity_terms", 0))
+    out.gk_table_len = int(vent.get("gk_table_len", 0))
+    out.gk_factor, out.gk_top = float(vent.get("gk_factor", 0)), float(vent.get("gk_top", 0))
+    # (the kernels index these by the counts above: too short an array would be read past its end)
+    needs = {"velocity_params": {1: 5, 2: 2 * out.velocity_terms}.get(out.velocity_law, 0),
+             "gk_a": out.gk_table_len, "gk_b": out.gk_table_len}
+    for name in ("velocity_params", "gk_a", "gk_b"):
+        array = vent.get(name)
+        if array is not None and engine.size(array) < needs[name]:
+            raise ValueError(f"parcel: vent[{name!r}] must hold {needs[name]} values")
+        setattr(out, name, _address(array, FLOAT))
+    for name, size, dtype in (("air_density", n_parcel, FLOAT),
+                              ("air_dynamic_viscosity", n_parcel, FLOAT),
+                              ("reynolds_number", n_sd, FLOAT), ("out_of_table", n_parcel, INT)):
+        array = vent.get(name)
+        if array is not None and engine.size(array) != size:
+            raise ValueError(f"parcel: vent[{name!r}] must hold {size} values")
+        setattr(out, name, _address(array, dtype))
+    return out
 
 
 def _chem_profile_struct(engine, profile, n_rows):
@@ -217,26 +288,36 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
     def __init__(self, engine, formulae, setup, *, dt, T0, p0, qv0, w, mass_of_dry_air, z0=0,
                  counts, multiplicity, water_mass, dry_volume, kappa, f_org=None, route="fused",
                  steps_per_launch=0, general=False, chemistry=None, mole_fractions=None,
-                 dry_rho=None, dry_molar_mass=None, initial_moles=None, molar_mass=None):
+                 dry_rho=None, dry_molar_mass=None, initial_moles=None, molar_mass=None,
+                 terminal_velocity=None, descriptor=None):
+        """`terminal_velocity`: a name or a law object of pysdm_amd.terminal_velocity, needed
+        (and read) with a ventilation other than Neglect only.  `descriptor`: one of
+        `condensation.descriptor_of` instead of the formulae's own (a ventilation a `Formulae`
+        refuses travels so)"""
         if route not in ROUTES:
             raise ValueError(f"route must be one of {ROUTES}, not {route!r}")
         check_hydrostatics(formulae)
         self.engine, self.formulae, self.setup = engine, formulae, setup
-        self.descriptor = check_formulae(formulae)
-        self.ventilated = _option_name(formulae.ventilation) != "Neglect"
-        if route == "fused":
-            if engine.parcel_library is None:
-                raise NotImplementedError(
-                    f"engine `{engine.name}` has no parcel library: route='fused' is not "
-                    "available on it (route='stages' is)")
-            if self.ventilated:
-                raise NotImplementedError(
-                    "ventilation other than Neglect needs a fall velocity per droplet per step: "
-                    "it stays on route='stages'")
-        elif self.ventilated:
+        self.descriptor = check_formulae(formulae) if descriptor is None else descriptor
+        self.ventilated = self.descriptor.option[_VENT] != 0
+        self.terminal_velocity = None
+        if route == "fused" and engine.parcel_library is None:
             raise NotImplementedError(
-                "the parcel's stage route with ventilation needs a terminal velocity law: use "
-                "CondensationRunner with a Population")
+                f"engine `{engine.name}` has no parcel library: route='fused' is not "
+                "available on it (route='stages' is)")
+        if self.ventilated:
+            if terminal_velocity is None:
+                raise NotImplementedError(
+                    "a parcel with a ventilation other than Neglect needs a fall velocity per "
+                    "droplet per step: pass terminal_velocity=")
+            if chemistry is not None:
+                raise NotImplementedError(
+                    "parcel with chemistry: a ventilation other than Neglect is not served")
+            if route == "fused" and engine.parcel_vent_library is None:
+                raise NotImplementedError(
+                    f"engine `{engine.name}` has no library for the ventilated parcel: "
+                    "route='fused' is not available on it (route='stages' is)")
+            self.terminal_velocity = tv.make_law(terminal_velocity, engine, formulae.constants)
         if setup.dt_cond_range[0] == 0:
             raise NotImplementedError("dt_cond_range[0] == 0")
         self.chemistry = chemistry
@@ -308,6 +389,13 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
                             float)
         self.f_org = column(np.zeros(n_sd) if f_org is None else f_org, "f_org", float)
         self.critical_volume = engine.full(n_sd, FLOAT, np.nan)
+        if self.ventilated:  # Parcel.register -> Moist.sync: the air of the initial state
+            self.state.update({name: engine.empty(n_parcel, FLOAT) for name in VENT_STATE})
+            self._sync_air(self.state["air_density"], self.state["air_dynamic_viscosity"],
+                           self.state["rhod"], self.state["qv"], self.state["T"], n_parcel)
+            self.reynolds_number = engine.full(n_sd, FLOAT, np.nan)
+            self.out_of_table = engine.zeros(n_parcel, INT)
+            self._vent_law = vent_law(engine, self.terminal_velocity)
         if chemistry is not None:
             self._init_chemistry(mole_fractions, dry_rho, dry_molar_mass, initial_moles,
                                  molar_mass, np.ascontiguousarray(dry_volume, dtype=float),
@@ -485,7 +573,9 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
         second: (profile, chemistry profile) or (profile, chemistry profile, products).  Raises
         RuntimeError("Condensation failed", parcel, step) after the call for the first parcel whose
         solver failed in it: the other parcels' state stays valid (and the profile is kept in
-        `last_profile`); a failed parcel is skipped from then on"""
+        `last_profile`); a failed parcel is skipped from then on.  A ventilated parcel stopped by
+        the range of the Gunn-Kinzer table (a radius above its top) is such a parcel too, but
+        raises the ValueError of `GunnKinzerTable.evaluate`"""
         n_steps = int(n_steps)
         if n_steps < 0:
             raise ValueError("n_steps must not be negative")
@@ -516,7 +606,8 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
                             w_mid=eng.upload(w_mid.reshape(-1)), profile=record,
                             descriptor=self.descriptor, general=self.general,
                             requests=None if table is None else table.c_struct(), diag=diag,
-                            chem=None if self.chemistry is None else self._chem_call(chem_record))
+                            chem=None if self.chemistry is None else self._chem_call(chem_record),
+                            vent=self._vent_call() if self.ventilated else None)
             else:
                 self._run_stages(w_mid, record, table, diag, chem_record)
             self.n_steps += n_steps
@@ -549,10 +640,47 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
         for parcel in np.flatnonzero(failed >= 0):
             if int(parcel) not in self._reported:
                 self._reported.update(int(p) for p in np.flatnonzero(failed >= 0))
+                if self.ventilated and eng.download(self.out_of_table)[parcel]:
+                    self._raise_out_of_table(int(parcel))
                 raise RuntimeError("Condensation failed", int(parcel), int(failed[parcel]))
         if self.chemistry is not None:
             return (out, chem_out) if table is None else (out, chem_out, values)
         return out if table is None else (out, values)
+
+    # ---- ventilation (include/sdm_parcel_vent.h) ---------------------------------------------------
+    def _sync_air(self, air_density, air_dynamic_viscosity, rhod, qv, T, n):
+        """what Moist.sync leaves in the environment's "air density" and "air dynamic viscosity"
+        (moist.py:73-100), with the stage symbols"""
+        eng = self.engine
+        consts = [float(getattr(self.formulae.constants, name)) for name in CONSTANT_NAMES]
+        eng.call_condensation("sdm_air_density", air_density, rhod, qv, n)
+        eng.call_condensation("sdm_air_dynamic_viscosity", air_dynamic_viscosity, T, n, consts)
+
+    def _radius(self, out, mass, n):
+        """attributes/physics/radius.py of water masses, with the symbols `Population.radius`
+        launches"""
+        eng, const = self.engine, self.formulae.constants
+        eng.call("sdm_volume_of_water_mass", out, mass, n, float(const.rho_w))
+        eng.call("sdm_elementwise_f64", 2, out, out, None, 1 / float(const.PI_4_3), n)
+        eng.call("sdm_elementwise_f64", 4, out, out, None, 1 / 3, n)
+
+    def _largest_radius(self, radius, n):
+        return self.engine.scalar_out("sdm_reduce_f64", ctypes.c_double, 1, radius, n)
+
+    def _vent_call(self):
+        return {**self._vent_law, "air_density": self.state["air_density"],
+                "air_dynamic_viscosity": self.state["air_dynamic_viscosity"],
+                "reynolds_number": self.reynolds_number, "out_of_table": self.out_of_table}
+
+    def _raise_out_of_table(self, parcel):
+        """what GunnKinzerTable.evaluate raises for the radii that stopped `parcel` (its water
+        masses are those of before the step)"""
+        r0, r1 = (int(v) for v in self.parcel_start_host[parcel:parcel + 2])
+        radius = self.engine.empty(r1 - r0, FLOAT)
+        self._radius(radius, self.water_mass[r0:r1], r1 - r0)
+        raise ValueError(f"Radii can be interpolated up to {self.terminal_velocity.maximum_radius}"
+                         f" m (max value of {self._largest_radius(radius, r1 - r0)} m within "
+                         "input data)")
 
     def _latent_heat(self, T, scratch):
         """formulae.latent_heat_vapourisation.lv(T) in the library's arithmetic: Kirchhoff and
@@ -595,6 +723,14 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
         identity = eng.upload(np.arange(most, dtype=np.int64))
         dt_range = (setup.dt_cond_range[0], min(setup.dt_cond_range[1], self.dt))
         n_parcel = self.n_parcel
+        vent = self.ventilated
+        if vent:  # include/sdm_parcel_vent.h
+            air = {name: eng.empty(1, FLOAT) for name in
+                   ("rho", "eta", "new_rho", "new_eta", "T", "p", "RH")}
+            radius, velocity = eng.empty(most, FLOAT), eng.empty(most, FLOAT)
+            law = self.terminal_velocity
+            ranged = tv.law_name(law) == "GunnKinzer1949"  # (the closed forms have no range)
+            stopped = eng.download(self.out_of_table)
         with_chem = self.chemistry is not None
         if with_chem:
             chem_cfg = abi.ChemistryCfg.from_buffer_copy(self.chem_cfg)
@@ -629,6 +765,25 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
                                     ("pthd", thd), ("pqv", qv), ("T", T)):
                     eng.fill(one[name], value)
                 eng.fill(counters["n_substeps"], int(host["n_substeps"][c]))
+                if vent:
+                    # Moist.sync of this step: the pair the NEXT step reads, from the advanced
+                    # rhod and the thd and qv of before this step's condensation
+                    temperature_pressure_rh_call(eng, self.formulae, one["prhod"], one["thd"],
+                                                 one["qv"], air["T"], air["p"], air["RH"], 1)
+                    self._sync_air(air["new_rho"], air["new_eta"], one["prhod"], one["qv"],
+                                   air["T"], 1)
+                    self._radius(radius[:n], mass, n)
+                    if ranged and self._largest_radius(radius[:n], n) > law.maximum_radius:
+                        host["failed_step"][c] = host["steps_done"][c]
+                        stopped[c] = 1
+                        break
+                    law.evaluate(eng, velocity[:n], radius[:n], n,
+                                 *((False,) if ranged else ()))  # (check_range: done above)
+                    eng.fill(air["rho"], float(host["air_density"][c]))
+                    eng.fill(air["eta"], float(host["air_dynamic_viscosity"][c]))
+                    eng.call_condensation("sdm_reynolds_number", self.reynolds_number[r0:r1],
+                                          cell[:n], air["eta"], air["rho"], radius[:n],
+                                          velocity[:n], n)
                 eng.call("sdm_volume_of_water_mass", v_wet[:n], mass, n, float(const.rho_w))
                 eng.assign(backup[:n], mass)
                 critical_volume_call(eng, self.formulae, self.critical_volume[r0:r1],
@@ -643,8 +798,10 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
                     pthd=one["pthd"], predicted_water_vapour_mixing_ratio=one["pqv"],
                     kappa=self.kappa[r0:r1], f_org=self.f_org[r0:r1], rtol_x=setup.rtol_x,
                     rtol_thd=setup.rtol_thd, timestep=dt, counters=counters, cell_order=zero,
-                    RH_max=one["RH_max"], success=success, reynolds_number=None,
-                    air_density=None, air_dynamic_viscosity=None, dt_range=dt_range,
+                    RH_max=one["RH_max"], success=success,
+                    reynolds_number=self.reynolds_number[r0:r1] if vent else None,
+                    air_density=air["rho"] if vent else None,
+                    air_dynamic_viscosity=air["eta"] if vent else None, dt_range=dt_range,
                     adaptive=setup.adaptive, fuse=setup.fuse, multiplier=setup.multiplier,
                     RH_rtol=setup.RH_rtol, max_iters=setup.max_iters, general=self.general,
                     descriptor=self.descriptor)
@@ -667,6 +824,9 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
                 for name in ("n_activating", "n_deactivating", "n_ripening"):
                     host[name][c] = eng.download(counters[name])[0]
                 host["steps_done"][c] += 1
+                if vent:
+                    host["air_density"][c] = eng.download(air["new_rho"])[0]
+                    host["air_dynamic_viscosity"][c] = eng.download(air["new_eta"])[0]
                 for name, row in rows.items():
                     if row is not None:
                         row[k * n_parcel + c] = host[name][c]
@@ -715,6 +875,8 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
                     eng.assign(dst, eng.upload(src))
         for name, array in self.state.items():
             eng.assign(array, eng.upload(host[name]))
+        if vent:
+            eng.assign(self.out_of_table, eng.upload(stopped))
         for name, row in rows.items():
             if row is not None:
                 eng.assign(record[name], eng.upload(row))
@@ -730,6 +892,9 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
         out["water_mass"] = down(self.water_mass)
         out["critical_volume"] = down(self.critical_volume)
         out["n_steps"] = self.n_steps
+        if self.ventilated:  # (the carried air pair is among the state arrays)
+            out["reynolds_number"] = down(self.reynolds_number)
+            out["out_of_table"] = down(self.out_of_table)
         if self.chemistry is not None:
             out.update(self._chem_columns(down))
         return out
@@ -754,12 +919,15 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
                 self.n_steps = int(value)
                 continue
             columns = {"water_mass": self.water_mass, "critical_volume": self.critical_volume}
+            if self.ventilated:
+                columns.update(reynolds_number=self.reynolds_number,
+                               out_of_table=self.out_of_table)
             if self.chemistry is not None:
                 columns.update(self._chem_columns())
             target = columns.get(name, self.state.get(name))
             if target is None:
                 raise KeyError(name)
-            dtype = INT if name in _INT_FIELDS + CHEM_COUNTERS else \
+            dtype = INT if name in _INT_FIELDS + CHEM_COUNTERS + ("out_of_table",) else \
                 np.uint8 if name == "do_chemistry_flag" else FLOAT
             value = np.ascontiguousarray(np.broadcast_to(
                 np.asarray(value, dtype=dtype), (eng.size(target),)))

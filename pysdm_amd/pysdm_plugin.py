@@ -522,6 +522,11 @@ def run_parcel(particulator, steps, products=()):
     does not converge, a negative amount, a gas taken beyond what the parcel holds) raises
     afterwards.  Any other set of dynamics is refused.
 
+    Formulae with a ventilation other than Neglect go to `sdm_parcel_run_vent`
+    (include/sdm_parcel_vent.h) with the law of `velocity_law_from_pysdm`; the environment's
+    current "air density" and "air dynamic viscosity" are the carried pair, read and left as
+    `Moist.sync` leaves them.  Not with AqueousChemistry.
+
     Observers and PySDM's own product objects are NOT notified per step.  `products` (objects of
     pysdm_amd.products, which carry PySDM's names, arguments and units) are evaluated inside the
     kernel's step loop after every step (`sdm_parcel_run_diag`, include/sdm_parcel_diag.h).
@@ -550,9 +555,11 @@ def run_parcel(particulator, steps, products=()):
         return None
     formulae, eng = particulator.formulae, particulator.backend.engine
     _parcel.check_hydrostatics(formulae)
-    if _parcel._option_name(formulae.ventilation) != "Neglect":  # pylint: disable=protected-access
-        raise ValueError("run_parcel: ventilation other than Neglect stays on particulator.run")
     descriptor = check_formulae(formulae)
+    ventilated = descriptor.option[_parcel._VENT] != 0  # pylint: disable=protected-access
+    if ventilated and with_chem:
+        raise ValueError("run_parcel: AqueousChemistry with a ventilation other than Neglect "
+                         "stays on particulator.run")
     setup = CondensationSetup(
         rtol_x=dynamic.rtol_x, rtol_thd=dynamic.rtol_thd,
         dt_cond_range=tuple(dynamic.dt_cond_range), adaptive=bool(dynamic.adaptive),
@@ -626,8 +633,20 @@ def run_parcel(particulator, steps, products=()):
             "mixing_ratios": ratios, "consts": _chem.constants_of(formulae),
             "dry_factor": float(aqueous.dry_molar_mass) / float(aqueous.dry_rho),
             "counters": chem_counters, "profile": None}
+    vent = None
+    if ventilated:  # include/sdm_parcel_vent.h: the law of the formulae, the environment's air
+        from .terminal_velocity import make_law  # pylint: disable=import-outside-toplevel
+
+        if eng.parcel_vent_library is None:
+            raise NotImplementedError(
+                f"engine `{eng.name}` has no library for the ventilated parcel")
+        law = make_law(velocity_law_from_pysdm(formulae), eng, formulae.constants)
+        out_of_table = eng.zeros(1, INT)
+        vent = {**_parcel.vent_law(eng, law), "air_density": current["air density"].data,
+                "air_dynamic_viscosity": current["air dynamic viscosity"].data,
+                "reynolds_number": eng.empty(n_sd, FLOAT), "out_of_table": out_of_table}
     _parcel.parcel_call(
-        eng, formulae, cfg, n_steps=steps, chem=chem_call,
+        eng, formulae, cfg, n_steps=steps, chem=chem_call, vent=vent,
         parcel_start=eng.upload(np.array([0, n_sd], dtype=np.int64)),
         water_mass=attrs["signed water mass"].data, multiplicity=attrs["multiplicity"].data,
         dry_volume=attrs["dry volume"].data, kappa=attrs["kappa"].data,
@@ -663,6 +682,10 @@ def run_parcel(particulator, steps, products=()):
         eng.fill(dynamic.success.data, True)
         particulator.n_steps += done
     if done < steps:
+        if ventilated and int(eng.download(out_of_table)[0]):
+            # (what the table's `evaluate` raises in particulator.run, before the dynamic ran)
+            raise ValueError(f"Radii can be interpolated up to {law.maximum_radius} m: a radius "
+                             f"above it stopped the parcel in step {done} of this call")
         eng.fill(dynamic.success.data, False)
         raise RuntimeError("Condensation failed")
     if with_chem:

@@ -31,6 +31,13 @@ the fused route (`sdm_parcel_run_chem`: per step one launch of the parcel kernel
 k_parcel_chem) at 1, 16, 256 and 1024 parcels, the stage route (the stage step, then
 `sdm_chemistry_step` on the parcel's slice and the two element-wise updates) at 1 and 16, and the
 same ascents without chemistry on the same build.  Writes profiles/parcel_chem_timing.json.
+
+`--ventilation` is a further measurement of its own: the ventilated parcel
+(include/sdm_parcel_vent.h; PySDM's default formulae with the ventilation
+PruppacherAndRasmussen1979 and the Gunn-Kinzer table): the fused route (`sdm_parcel_run_vent`)
+against the fused route with the ventilation Neglect (through k_parcel and through k_parcel_f) at
+1, 16, 256 and 1024 parcels, and against the ventilated stage route at 1 and 16.  Writes
+profiles/parcel_vent_timing.json with the ratios; no threshold.
 """
 import argparse
 import json
@@ -246,6 +253,74 @@ def main_chemistry(args):
     print("wrote", out)
 
 
+VENTILATION, VENTILATION_LAW = "PruppacherAndRasmussen1979", "GunnKinzer1949"
+
+
+def measure_ventilation(mode, n_parcel, route, reps, warmup):
+    """`mode`: "ventilated" (k_parcel_v), "neglect" (PySDM's defaults: k_parcel) or
+    "neglect-general" (the same through the general kernel k_parcel_f, which k_parcel_v extends)"""
+    from pysdm_amd import spectra  # pylint: disable=import-outside-toplevel
+    from pysdm_amd.condensation import CondensationSetup  # pylint: disable=import-outside-toplevel
+    from pysdm_amd.engine import HipEngine  # pylint: disable=import-outside-toplevel
+    from pysdm_amd.formulae import Formulae  # pylint: disable=import-outside-toplevel
+    from pysdm_amd.parcel import ParcelRunner  # pylint: disable=import-outside-toplevel
+
+    ventilated = mode == "ventilated"
+    formulae = Formulae(ventilation=VENTILATION) if ventilated else Formulae()
+    updrafts = np.linspace(0.2, 5.0, n_parcel) if n_parcel > 1 else np.array([2.0])
+    runner = ParcelRunner.from_spectrum(
+        HipEngine.get(), formulae, CondensationSetup(), dt=DT, T0=290.0, p0=100000.0, qv0=0.012,
+        w=updrafts, mass_of_dry_air=1.0,
+        spectrum=spectra.Lognormal(norm_factor=60e6 / 1.18, m_mode=0.04e-6, s_geom=1.4),
+        kappa=1.28, n_sd=N_SD, n_parcel=n_parcel, route=route, general=mode == "neglect-general",
+        terminal_velocity=VENTILATION_LAW if ventilated else None)
+    start = runner.snapshot()
+    samples = timed(runner, start, STEPS, reps, warmup)
+    final = runner.snapshot()
+    assert (final["failed_step"] == -1).all() and (final["steps_done"] == STEPS).all()
+    ms = float(np.median(samples))
+    out = {"mode": mode, "route": route, "n_parcel": n_parcel, "n_sd_per_parcel": N_SD,
+           "steps": STEPS, "reps": reps, "ms_median": round(ms, 3),
+           "ms_min": round(float(np.min(samples)), 3), "ms_max": round(float(np.max(samples)), 3),
+           "ms_per_parcel_step": round(ms / (n_parcel * STEPS), 5)}
+    if ventilated:
+        out["reynolds_number_max_last"] = float(final["reynolds_number"].max())
+    return out
+
+
+def main_ventilation(args):
+    results = []
+    for mode in ("neglect", "neglect-general", "ventilated"):
+        for n_parcel in SIZES:
+            results.append(measure_ventilation(mode, n_parcel, "fused", args.reps, args.warmup))
+            print(json.dumps(results[-1]), flush=True)
+    for n_parcel in STAGE_SIZES:
+        results.append(measure_ventilation("ventilated", n_parcel, "stages", args.reps,
+                                           args.warmup))
+        print(json.dumps(results[-1]), flush=True)
+    by = {(r["mode"], r["route"], r["n_parcel"]): r["ms_median"] for r in results}
+    ratios = {
+        "fused ventilated / fused neglect": {
+            str(n): round(by["ventilated", "fused", n] / by["neglect", "fused", n], 3)
+            for n in SIZES},
+        "fused ventilated / fused neglect-general": {
+            str(n): round(by["ventilated", "fused", n] / by["neglect-general", "fused", n], 3)
+            for n in SIZES},
+        "stages ventilated / fused ventilated": {
+            str(n): round(by["ventilated", "stages", n] / by["ventilated", "fused", n], 3)
+            for n in STAGE_SIZES}}
+    out = args.out or os.path.join(ROOT, "profiles", "parcel_vent_timing.json")
+    with open(out, "w", encoding="utf-8") as handle:
+        handle.write(json.dumps({
+            "workload": f"{N_SD} super-droplets per parcel, {STEPS} steps of {DT} s, updrafts "
+                        f"0.2 .. 5 m/s (2 m/s for one parcel); PySDM's default formulae, with "
+                        f"ventilation {VENTILATION} and the law {VENTILATION_LAW} or without; HIP "
+                        f"events, median of {args.reps} after {args.warmup} warm-up call(s)",
+            "results": results, "ratios": ratios}, indent=1) + "\n")
+    print(json.dumps(ratios))
+    print("wrote", out)
+
+
 def main():
     parser = argparse.ArgumentParser()
     parser.add_argument("--reps", type=int, default=5)
@@ -259,7 +334,12 @@ def main():
     parser.add_argument("--products-stepwise-only", action="store_true")
     parser.add_argument("--chemistry", action="store_true",
                         help="time the parcel with aqueous chemistry instead (see the docstring)")
+    parser.add_argument("--ventilation", action="store_true",
+                        help="time the ventilated parcel instead (see the docstring)")
     args = parser.parse_args()
+    if args.ventilation:
+        main_ventilation(args)
+        return
     if args.chemistry:
         main_chemistry(args)
         return
