@@ -47,6 +47,8 @@ PARCEL_DIAG_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "sdm_p
 PARCEL_CHEM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "sdm_parcel_chem.h")
 # and the ventilated parcel (Reynolds numbers inside the step loop)
 PARCEL_VENT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "sdm_parcel_vent.h")
+# and the parcel with coalescence (condensation and collisions in one call)
+PARCEL_COAL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "sdm_parcel_coal.h")
 # SDM_HIP_LIB: another build of the same library (tuning variants); still no fallback
 HIP_LIB_PATH = os.environ.get("SDM_HIP_LIB") or os.path.join(_HERE, "libsdm_hip.so")
 
@@ -235,6 +237,25 @@ class ParcelVent(ctypes.Structure):  # == sdm_parcel_vent (include/sdm_parcel_ve
     ]
 
 
+# include/sdm_parcel_coal.h: SDM_PARCEL_COAL_*
+PARCEL_COAL_MAX_ROWS, PARCEL_COAL_MAX_GRID = 2048, 1024
+PARCEL_COAL_EVENT_BOUND, PARCEL_COAL_EVENT_DT_MIN, PARCEL_COAL_OVERFLOW_SHIFT = 0x1, 0x100, 32
+PARCEL_COAL_STATE_FIELDS = ("idx", "n_live", "kappa_times_dry_volume", "collision_rate",
+                            "collision_rate_deficit", "coalescence_rate", "stats_n_substep",
+                            "stats_dt_min", "events", "rng_offset", "rng_state_inc", "gk_a", "gk_b",
+                            "velocity_params")
+PARCEL_COAL_PROFILE_FIELDS = ("n_live", "n_substeps", "coalescence_rate",
+                              "collision_rate_deficit", "dv")
+
+
+class ParcelCoalState(ctypes.Structure):  # == sdm_parcel_coal_state (include/sdm_parcel_coal.h)
+    _fields_ = [(name, c_ptr) for name in PARCEL_COAL_STATE_FIELDS]
+
+
+class ParcelCoalProfile(ctypes.Structure):  # == sdm_parcel_coal_profile
+    _fields_ = [(name, c_ptr) for name in PARCEL_COAL_PROFILE_FIELDS]
+
+
 class RelaxedVelocityCfg(ctypes.Structure):  # == sdm_relaxed_velocity_cfg
     _fields_ = [
         ("n_sd", c_i64), ("gk_table_len", c_i64), ("dt", c_f64), ("c", c_f64), ("rho_w", c_f64),
@@ -414,6 +435,7 @@ _parcel_library = None
 _parcel_diag_library = None
 _parcel_chem_library = None
 _parcel_vent_library = None
+_parcel_coal_library = None
 
 
 def hip_library():
@@ -530,6 +552,15 @@ def parcel_vent_library():
         _parcel_vent_library = Library(HIP_LIB_PATH, "the HIP kernels of pysdm_amd",
                                        header=PARCEL_VENT_HEADER_PATH)
     return _parcel_vent_library
+
+
+def parcel_coal_library():
+    """libsdm_hip.so bound to include/sdm_parcel_coal.h (same file, same contexts)"""
+    global _parcel_coal_library  # pylint: disable=global-statement
+    if _parcel_coal_library is None:
+        _parcel_coal_library = Library(HIP_LIB_PATH, "the HIP kernels of pysdm_amd",
+                                       header=PARCEL_COAL_HEADER_PATH)
+    return _parcel_coal_library
 
 
 def pcg64_state_inc(seed):

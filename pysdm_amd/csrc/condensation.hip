@@ -173,6 +173,11 @@ __global__ __launch_bounds__(COND_CB) void k_parcel_d(ParcelArgs<DefaultFormulae
                                                       ParcelDiag d) {
   parcel_steps<DefaultFormulae, true>(a, &d);
 }
+// include/sdm_parcel_coal.h: the step over the parcel's live rows in the order of its permutation
+__global__ __launch_bounds__(COND_CB) void k_parcel_p(ParcelArgs<DefaultFormulae> a,
+                                                      ParcelPerm pp) {
+  parcel_steps<DefaultFormulae, false, false, true>(a, nullptr, nullptr, &pp);
+}
 __global__ __launch_bounds__(COND_CB) void k_parcel_diagnose(
     ParcelDiagnoseArgs<DefaultFormulae> a) {
   parcel_diagnose_cells<DefaultFormulae>(a);
@@ -258,6 +263,19 @@ int sdm_parcel_launch_default(sdm_ctx *ctx, const ParcelCall &call) {
   } else {
     hipLaunchKernelGGL(k_parcel, dim3((unsigned)call.n_parcel), dim3(COND_CB), 0, ctx->stream, a);
   }
+  LAUNCH_CHECK();
+  return SDM_OK;
+}
+
+int sdm_parcel_launch_default_perm(sdm_ctx *ctx, const ParcelCall &call, const int64_t *n_live,
+                                   double *dv) {
+  ParcelArgs<DefaultFormulae> a;
+  SDM_PARCEL_FILL_ARGS(a, call);
+  a.c.k = consts_of(call.consts);
+  ARG_TRY(n_live && dv && !call.requests);
+  const ParcelPerm pp{n_live, dv};
+  hipLaunchKernelGGL(k_parcel_p, dim3((unsigned)call.n_parcel), dim3(COND_CB), 0, ctx->stream, a,
+                     pp);
   LAUNCH_CHECK();
   return SDM_OK;
 }

@@ -191,6 +191,11 @@ __global__ __launch_bounds__(COND_CB) void k_parcel_f_d(ParcelArgs<GeneralFormul
                                                         ParcelDiag d) {
   parcel_steps<GeneralFormulae, true>(a, &d);
 }
+// include/sdm_parcel_coal.h: the step over the parcel's live rows in the order of its permutation
+__global__ __launch_bounds__(COND_CB) void k_parcel_f_p(ParcelArgs<GeneralFormulae> a,
+                                                        ParcelPerm pp) {
+  parcel_steps<GeneralFormulae, false, false, true>(a, nullptr, nullptr, &pp);
+}
 // include/sdm_parcel_vent.h: the general formulae for a parcel whose air density and viscosity
 // change from step to step inside the kernel - the solver's cell scalars read the parcel's pair
 // from LDS (parcel_solver.h), everything else is GeneralFormulae's
@@ -306,6 +311,26 @@ int sdm_parcel_launch_general(sdm_ctx *ctx, const ParcelCall &call,
     hipLaunchKernelGGL(k_parcel_f, dim3((unsigned)call.n_parcel), dim3(COND_CB), 0, ctx->stream,
                        a);
   }
+  LAUNCH_CHECK();
+  return SDM_OK;
+}
+
+int sdm_parcel_launch_general_perm(sdm_ctx *ctx, const ParcelCall &call,
+                                   const sdm_cond_formulae *formulae, const int64_t *n_live,
+                                   double *dv) {
+  ParcelArgs<GeneralFormulae> a;
+  SDM_PARCEL_FILL_ARGS(a, call);
+  ARG_TRY(formulae && formulae_of(call.consts, formulae, &a.c.k.f));
+  ARG_TRY(formulae->option[SDM_COND_OPT_VENTILATION] == SDM_COND_VENT_NEGLECT);
+  ARG_TRY(formulae->option[SDM_COND_OPT_SURFACE_TENSION] == SDM_COND_SGM_CONSTANT || call.f_org);
+  ARG_TRY(n_live && dv && !call.requests);
+  a.c.k.f_org = call.f_org;
+  a.c.k.reynolds_number = nullptr;
+  a.c.k.vdry = call.vdry;
+  a.c.k.air_density = a.c.k.air_dynamic_viscosity = nullptr;
+  const ParcelPerm pp{n_live, dv};
+  hipLaunchKernelGGL(k_parcel_f_p, dim3((unsigned)call.n_parcel), dim3(COND_CB), 0, ctx->stream,
+                     a, pp);
   LAUNCH_CHECK();
   return SDM_OK;
 }

@@ -88,6 +88,14 @@ int sdm_parcel_prepare(sdm_ctx *ctx, const sdm_parcel_cfg *cfg, int64_t n_steps,
 int sdm_parcel_launch_default(sdm_ctx *ctx, const ParcelCall &call);
 int sdm_parcel_launch_general(sdm_ctx *ctx, const ParcelCall &call,
                               const sdm_cond_formulae *formulae);
+// ... and of their siblings over a real permutation (include/sdm_parcel_coal.h: k_parcel_p,
+// k_parcel_f_p): `call.identity` then holds the caller's permutation of global row numbers,
+// `n_live` the live positions per parcel, and `dv` (n_parcel doubles) takes the step's dv
+int sdm_parcel_launch_default_perm(sdm_ctx *ctx, const ParcelCall &call, const int64_t *n_live,
+                                   double *dv);
+int sdm_parcel_launch_general_perm(sdm_ctx *ctx, const ParcelCall &call,
+                                   const sdm_cond_formulae *formulae, const int64_t *n_live,
+                                   double *dv);
 // condensation_formulae.hip: one launch of the ventilated kernel (include/sdm_parcel_vent.h;
 // `vent` was checked by the caller)
 int sdm_parcel_launch_vent(sdm_ctx *ctx, const ParcelCall &call,
@@ -306,9 +314,21 @@ DF double vent_velocity(const ParcelVent &v, double r) {
   return power_series_velocity(r, v.terms, v.params, v.params + v.terms);
 }
 
-template <class P, bool DIAG = false, bool VENT = false>
+// ---- a real permutation (include/sdm_parcel_coal.h) ---------------------------------------------
+// parcel_steps<P, false, false, true> (k_parcel_p, k_parcel_f_p) carries the step out over the
+// parcel's LIVE rows in the order of its permutation: position q of the parcel is row
+// idx[parcel_start[c] + q] (a global row number, as the identity's entries are), q < n_live[c].
+// The solver always went through `cidx`; here the row loops around it do too.  Rows that are not
+// live are neither read nor written.  The step's dv goes to `dv[c]` for the collision kernel that
+// follows in the stream.
+struct ParcelPerm {
+  const int64_t *n_live;
+  double *dv;
+};
+
+template <class P, bool DIAG = false, bool VENT = false, bool PERM = false>
 DF void parcel_steps(const ParcelArgs<P> &a, const ParcelDiag *d = nullptr,
-                     const ParcelVent *v = nullptr) {
+                     const ParcelVent *v = nullptr, const ParcelPerm *pp = nullptr) {
   __shared__ double s_par[PS_N];
   __shared__ int64_t s_nsub;
   DiagLds dl;
@@ -319,9 +339,24 @@ DF void parcel_steps(const ParcelArgs<P> &a, const ParcelDiag *d = nullptr,
   const typename P::K &k = g.k;
   const int tid = (int)threadIdx.x;
   for (int64_t c = blockIdx.x; c < a.n_parcel; c += gridDim.x) {
-    const int64_t row0 = a.parcel_start[c], n = a.parcel_start[c + 1] - row0;
+    const int64_t row0 = a.parcel_start[c];
+    int64_t n = a.parcel_start[c + 1] - row0;
     // (checked on the host too; failed parcels are skipped for good)
     if (row0 < 0 || n <= 0 || row0 + n > g.n_sd || a.st.failed_step[c] >= 0) continue;
+    if constexpr (PERM) {  // the live positions (uniform over the workgroup)
+      const int64_t live = pp->n_live[c];
+      if (live <= 0 || live > n) continue;
+      n = live;
+    }
+    // the row at position q of the parcel (PERM: a word the host has checked, checked again here)
+    auto row_at = [&](int64_t q) -> int64_t {
+      if constexpr (PERM) {
+        const int64_t row = g.idx[row0 + q];
+        return row >= 0 && row < g.n_sd ? row : -1;
+      } else {
+        return row0 + q;
+      }
+    };
     CellSolver<P> cs{g, g.idx + row0, n, c, tid};
     attach_lds<P>(cs);
     __syncthreads();  // the previous parcel's reads of s_par are over
@@ -369,6 +404,8 @@ DF void parcel_steps(const ParcelArgs<P> &a, const ParcelDiag *d = nullptr,
             (a.g_std / T * rho * (Rq / cp - 1) - p * lv / cp / (T * T) * dql_dz) / Rq;
         prhod = rhod + a.dt * (w * drho_dz);
         dv = mass_of_dry_air / ((prhod + rhod) / 2);
+        if constexpr (PERM)
+          if (tid == 0) pp->dv[c] = dv;
         if (tid == 0) {
           s_par[PS_PZ] = s_par[PS_Z] + a.dt * w;  // (lane 0 alone reads these two again)
           s_par[PS_PRHOD] = prhod;
@@ -387,9 +424,12 @@ DF void parcel_steps(const ParcelArgs<P> &a, const ParcelDiag *d = nullptr,
         if (v->law == SDM_VELOCITY_LAW_GUNN_KINZER) {  // (uniform)
           const double inv_pi_4_3 = 1 / P::pi_4_3(k);
           bool over = false;
-          for (int64_t q = tid; q < n; q += COND_CB)
-            over = over || radius_of_volume(volume_of_mass(g.water_mass[row0 + q], P::rho_w(k)),
+          for (int64_t q = tid; q < n; q += COND_CB) {
+            const int64_t row = row_at(q);
+            if (PERM && row < 0) continue;
+            over = over || radius_of_volume(volume_of_mass(g.water_mass[row], P::rho_w(k)),
                                             inv_pi_4_3) > v->gk_top;
+          }
           if (over) vl->out_of_range = 1;
           __syncthreads();
           if (vl->out_of_range) {  // uniform; lane 0 clears the flag when it loads the next parcel
@@ -402,7 +442,8 @@ DF void parcel_steps(const ParcelArgs<P> &a, const ParcelDiag *d = nullptr,
       // the critical volume of every row at the parcel's temperature; the copy of the masses the
       // solver writes in place
       for (int64_t q = tid; q < n; q += COND_CB) {
-        const int64_t row = row0 + q;
+        const int64_t row = row_at(q);
+        if (PERM && row < 0) continue;
         const double m = g.water_mass[row];
         a.v_cr[row] = P::critical_volume(k, row, g.kappa[row], g.vdry[row], m / P::rho_w(k), T);
         if (q >= COND_CH) a.mass_backup[row] = m;
@@ -414,8 +455,11 @@ DF void parcel_steps(const ParcelArgs<P> &a, const ParcelDiag *d = nullptr,
       cs.init();
       const SolveOut s = solve_cell<P>(cs, g, thd, qv, rhod, prhod, thd, qv, dv, s_nsub);
       if (!s.o.success) {  // uniform: the solver's results come from LDS after a barrier
-        for (int64_t q = COND_CH + tid; q < n; q += COND_CB)
-          g.water_mass[row0 + q] = a.mass_backup[row0 + q];
+        for (int64_t q = COND_CH + tid; q < n; q += COND_CB) {
+          const int64_t row = row_at(q);
+          if (PERM && row < 0) continue;
+          g.water_mass[row] = a.mass_backup[row];
+        }
         failed = done;
         break;
       }

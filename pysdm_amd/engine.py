@@ -45,6 +45,8 @@ class Engine:
     parcel_chem_library = None
     # likewise include/sdm_parcel_vent.h
     parcel_vent_library = None
+    # likewise include/sdm_parcel_coal.h
+    parcel_coal_library = None
     # whether the fused collision step of `library` can take the fall velocity from the
     # "relative fall momentum" row; an engine that cannot must refuse, not ignore the request
     fused_momentum_velocity = False
@@ -178,6 +180,14 @@ class Engine:
         self._before_call()
         self.parcel_vent_library.invoke(symbol, self.handle, args)
 
+    def call_parcel_coal(self, symbol, *args):
+        """a symbol of include/sdm_parcel_coal.h"""
+        if self.parcel_coal_library is None:
+            raise NotImplementedError(
+                f"engine `{self.name}` has no library for the parcel with coalescence")
+        self._before_call()
+        self.parcel_coal_library.invoke(symbol, self.handle, args)
+
     def _before_call(self):
         pass
 
@@ -218,6 +228,7 @@ class HipEngine(Engine):
         self.parcel_diag_library = abi.parcel_diag_library()
         self.parcel_chem_library = abi.parcel_chem_library()
         self.parcel_vent_library = abi.parcel_vent_library()
+        self.parcel_coal_library = abi.parcel_coal_library()
         self.handle = abi.c_ptr()
         self.library.check(self.library.cdll.sdm_ctx_create(ctypes.byref(self.handle),
                                                             abi.c_int(device_index)))

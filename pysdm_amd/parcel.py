@@ -30,6 +30,7 @@ kernel's step loop (`sdm_parcel_run_diag`, include/sdm_parcel_diag.h), the stage
 `sdm_parcel_diagnose` after each step; `diagnose` gives the products of the current state.
 """
 import ctypes
+import warnings
 
 import numpy as np
 
@@ -52,6 +53,9 @@ _SGM = OPTION_ORDER.index("surface_tension")
 _VENT = OPTION_ORDER.index("ventilation")
 VENT_STATE = ("air_density", "air_dynamic_viscosity")  # what a ventilated parcel carries
 CHEM_COUNTERS = ("n_failed", "n_negative", "n_exceeded")
+COAL_COUNTERS = ("collision_rate", "collision_rate_deficit", "coalescence_rate")
+_COAL_INTS = ("out_of_table", "multiplicity", "idx", "n_live", "stats_n_substep", "events",
+              "rng_offset")
 _DIAG_LANES = 256  # the partials of the SUM of include/sdm_parcel_diag.h
 
 
@@ -97,7 +101,8 @@ def parcel_cfg(formulae, setup, dt, steps_per_launch=0):
 
 def parcel_call(engine, formulae, cfg, *, n_steps, parcel_start, water_mass, multiplicity,
                 dry_volume, kappa, f_org, critical_volume, state, w_mid, profile=None,
-                descriptor=None, general=False, requests=None, diag=None, chem=None, vent=None):
+                descriptor=None, general=False, requests=None, diag=None, chem=None, vent=None,
+                coal=None):
     """one `sdm_parcel_run` call with raw engine arrays: `state` / `profile` are dicts of engine
     arrays by the member names of sdm_parcel_state / sdm_parcel_profile (`profile` may be None or
     lack members), `w_mid` an engine array of n_steps x n_parcel.  PySDM's default formulae go to
@@ -113,7 +118,13 @@ def parcel_call(engine, formulae, cfg, *, n_steps, parcel_start, water_mass, mul
     the member names of sdm_parcel_vent - the law's part as `vent_law` builds it, and the engine
     arrays `air_density`, `air_dynamic_viscosity` (n_parcel each), `reynolds_number` (n_sd) and
     optionally `out_of_table` (n_parcel, int64); `descriptor` may then be one of
-    `condensation.descriptor_of` naming a ventilation a `Formulae` refuses"""
+    `condensation.descriptor_of` naming a ventilation a `Formulae` refuses.  With `coal` the call
+    is `sdm_parcel_run_coal` (include/sdm_parcel_coal.h): a dict with `cfg` (abi.StepCfg), the
+    engine arrays of sdm_parcel_coal_state by their member names (`rng_offset` and
+    `rng_state_inc` as int64 arrays holding the unsigned words; the fall-velocity members may be
+    missing), `fresh_idx` (default True) and `profile` (None, or a dict by the member names of
+    sdm_parcel_coal_profile; entries may be missing); `multiplicity`, `dry_volume` and `kappa`
+    are then written"""
     if descriptor is None:
         descriptor = check_formulae(formulae)
     if vent is not None and chem is not None:
@@ -140,6 +151,16 @@ def parcel_call(engine, formulae, cfg, *, n_steps, parcel_start, water_mass, mul
             parcel_start, water_mass, multiplicity, dry_volume, kappa, f_org, critical_volume,
             c_state, w_mid, c_profile, consts,
             None if is_default(descriptor) and not general else descriptor)
+    if coal is not None:
+        if requests is not None or chem is not None or vent is not None:
+            raise NotImplementedError("parcel with coalescence: no request table, chemistry or "
+                                      "ventilation in the same call")
+        engine.call_parcel_coal(
+            "sdm_parcel_run_coal", args[0], coal["cfg"], *args[1:],
+            _coal_state_struct(engine, coal, n_parcel, int(engine.size(water_mass))),
+            _coal_profile_struct(engine, coal.get("profile"), n_steps * n_parcel),
+            int(bool(coal.get("fresh_idx", True))))
+        return
     if requests is None and chem is None and vent is None:
         engine.call_parcel("sdm_parcel_run", *args)
         return
@@ -230,6 +251,40 @@ def _chem_profile_struct(engine, profile, n_rows):
     return out
 
 
+_COAL_FLOATS = ("kappa_times_dry_volume", "stats_dt_min", "gk_a", "gk_b", "velocity_params", "dv")
+
+
+def _coal_state_struct(engine, coal, n_parcel, n_sd):
+    """abi.ParcelCoalState of a dict of engine arrays by the member names"""
+    out = abi.ParcelCoalState()
+    sizes = {"idx": n_sd, "kappa_times_dry_volume": n_sd, "rng_state_inc": 4 * n_parcel}
+    for name in abi.PARCEL_COAL_STATE_FIELDS:
+        array = coal.get(name)
+        if name in ("gk_a", "gk_b", "velocity_params"):  # (sized by the cfg's counts)
+            setattr(out, name, _address(array, FLOAT))
+            continue
+        if array is None:
+            raise ValueError(f"parcel: coal[{name!r}] is missing")
+        if engine.size(array) != sizes.get(name, n_parcel):
+            raise ValueError(f"parcel: coal[{name!r}] must hold {sizes.get(name, n_parcel)} "
+                             "values")
+        setattr(out, name, _address(array, FLOAT if name in _COAL_FLOATS else INT))
+    return out
+
+
+def _coal_profile_struct(engine, profile, n_rows):
+    """abi.ParcelCoalProfile of a dict of engine arrays (None: no record)"""
+    if profile is None:
+        return None
+    out = abi.ParcelCoalProfile()
+    for name in abi.PARCEL_COAL_PROFILE_FIELDS:
+        array = profile.get(name)
+        if array is not None and engine.size(array) != n_rows:
+            raise ValueError(f"parcel: a coalescence profile member must hold {n_rows} values")
+        setattr(out, name, _address(array, FLOAT if name in _COAL_FLOATS else INT))
+    return out
+
+
 def diag_sum(multiplicity, values):
     """the SUM of include/sdm_parcel_diag.h of multiplicity * values on the host, add for add"""
     terms = np.asarray(multiplicity).astype(float) * np.asarray(values, dtype=float)
@@ -277,6 +332,64 @@ def diagnose_call(engine, formulae, requests, *, parcel_start, water_mass, multi
         _diag_struct(engine, {k: v for k, v in diag.items() if k != "dv"}, sizes, n_parcel))
 
 
+def check_collisions(collisions, counts):
+    """what `sdm_parcel_run_coal` refuses of a `recipe.CollisionSetup` and of the parcels' sizes,
+    refused by name"""
+    if collisions.breakup:
+        raise NotImplementedError("parcel with coalescence: breakup is not served "
+                                  "(CollisionSetup.coalescence only)")
+    if collisions.optimized_random:
+        raise NotImplementedError("parcel with coalescence: optimized_random is not served")
+    if collisions.croupier != "local":
+        raise NotImplementedError("parcel with coalescence: the global croupier is not "
+                                  "served (a parcel is one cell: croupier='local')")
+    most = int(np.max(np.asarray(counts, dtype=np.int64), initial=0))
+    if most > abi.PARCEL_COAL_MAX_ROWS:
+        raise ValueError(f"parcel with coalescence: a parcel of {most} rows, more than "
+                         f"SDM_PARCEL_COAL_MAX_ROWS = {abi.PARCEL_COAL_MAX_ROWS}")
+
+
+def collision_cfg(engine, collisions, dt, rho_w, terminal_velocity=None):
+    """(the `sdm_step_cfg` of a CollisionSetup of coalescence for `sdm_parcel_run_coal` and the
+    stage route - the parcel's rows, dv and stream are filled in per parcel -, the law's members
+    as `vent_law` builds them or None, the clamped dt_coal_range)"""
+    from .physics import constants as physics_constants  # pylint: disable=import-outside-toplevel
+
+    k = physics_constants.namespace()
+    desc = collisions.descriptor(k)
+    law = None
+    dt_range = collisions.clamped_dt_range(dt)
+    cfg = abi.StepCfg()
+    cfg.n_cell, cfg.n_attr, cfg.mass_attr = 1, 3, 0
+    cfg.dt = dt
+    cfg.dt_min, cfg.dt_max = dt_range
+    cfg.adaptive, cfg.substeps = int(collisions.adaptive), int(collisions.substeps)
+    cfg.croupier_local = int(collisions.croupier == "local")
+    cfg.optimized_random = int(collisions.optimized_random)
+    cfg.enable_breakup = int(collisions.breakup)
+    cfg.kernel = desc.get("kernel", 0)
+    for name, width in (("kernel_param", 2), ("kernel_berry_params", 13)):
+        setattr(cfg, name, (abi.c_f64 * width)(*desc.get(name, (0.0,) * width)))
+    cfg.kernel_berry_unit = desc.get("kernel_berry_unit", 1.0)
+    cfg.berry_unit = 1.0
+    cfg.frag_nfmax = -1.0
+    cfg.rho_w, cfg.sgm_w = rho_w, k.sgm_w
+    cfg.max_multiplicity = int(collisions.max_multiplicity)
+    if desc["needs_gk"]:
+        name = tv.law_name(terminal_velocity or "GunnKinzer1949")
+        if name not in engine.fused_velocity_laws:
+            raise NotImplementedError(
+                f"the fused collision step of engine `{engine.name}` does not evaluate the "
+                f"terminal-velocity law {name!r} (it has "
+                f"{', '.join(engine.fused_velocity_laws)})")
+        law = vent_law(engine, tv.make_law(terminal_velocity or "GunnKinzer1949", engine, k))
+        cfg.velocity_law = law["velocity_law"]
+        cfg.velocity_terms = law["velocity_terms"]
+        cfg.gk_table_len = law["gk_table_len"]
+        cfg.gk_factor = law["gk_factor"]
+    return cfg, law, dt_range
+
+
 class ParcelRunner:  # pylint: disable=too-many-instance-attributes
     """an ensemble of adiabatic parcels; see the module's docstring.
 
@@ -289,11 +402,14 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
                  counts, multiplicity, water_mass, dry_volume, kappa, f_org=None, route="fused",
                  steps_per_launch=0, general=False, chemistry=None, mole_fractions=None,
                  dry_rho=None, dry_molar_mass=None, initial_moles=None, molar_mass=None,
-                 terminal_velocity=None, descriptor=None):
+                 terminal_velocity=None, descriptor=None, collisions=None, seed=None):
         """`terminal_velocity`: a name or a law object of pysdm_amd.terminal_velocity, needed
-        (and read) with a ventilation other than Neglect only.  `descriptor`: one of
+        (and read) with a ventilation other than Neglect, and by the collision kernels that take
+        a fall velocity (the Gunn-Kinzer table if not given).  `descriptor`: one of
         `condensation.descriptor_of` instead of the formulae's own (a ventilation a `Formulae`
-        refuses travels so)"""
+        refuses travels so).  `collisions`: a `recipe.CollisionSetup` of coalescence as the third
+        dynamic (include/sdm_parcel_coal.h); `seed`: an int, or one per parcel (default: the
+        setup's), each parcel drawing from its own NumPy-PCG64 stream"""
         if route not in ROUTES:
             raise ValueError(f"route must be one of {ROUTES}, not {route!r}")
         check_hydrostatics(formulae)
@@ -305,6 +421,9 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
             raise NotImplementedError(
                 f"engine `{engine.name}` has no parcel library: route='fused' is not "
                 "available on it (route='stages' is)")
+        if self.ventilated and collisions is not None:
+            raise NotImplementedError(
+                "parcel with coalescence: a ventilation other than Neglect is not served")
         if self.ventilated:
             if terminal_velocity is None:
                 raise NotImplementedError(
@@ -335,6 +454,9 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
                     "chemistry: route='fused' is not available on it (route='stages' is)")
             if engine.chemistry_library is None:
                 raise NotImplementedError(f"engine `{engine.name}` has no chemistry library")
+        self.collisions = collisions
+        if collisions is not None:
+            self._check_collisions(collisions, route, counts)
         self.route, self.general = route, bool(general)
         self.dt = float(dt)
         self.cfg = parcel_cfg(formulae, setup, self.dt, steps_per_launch)
@@ -400,7 +522,12 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
             self._init_chemistry(mole_fractions, dry_rho, dry_molar_mass, initial_moles,
                                  molar_mass, np.ascontiguousarray(dry_volume, dtype=float),
                                  np.broadcast_to(np.asarray(kappa, dtype=float), (n_sd,)))
+        if collisions is not None:
+            self._init_collisions(collisions, seed, terminal_velocity,
+                                  np.ascontiguousarray(dry_volume, dtype=float),
+                                  np.broadcast_to(np.asarray(kappa, dtype=float), (n_sd,)))
         self.last_chem_profile = None
+        self.last_coal_profile = None
         self.n_steps = 0  # time steps asked for so far: the clock of w(t)
         self.last_profile = None
         self.last_products = None
@@ -448,6 +575,277 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
                 "moles": self.moles, "pH": self.pH, "do_chemistry_flag": self.do_chemistry_flag,
                 "mixing_ratios": self.mixing_ratios, "consts": self.chem_consts,
                 "dry_factor": self.dry_factor, "counters": self.chem_counters, "profile": record}
+
+    # ---- coalescence (include/sdm_parcel_coal.h) ------------------------------------------------
+    def _check_collisions(self, collisions, route, counts):
+        """what the library refuses is refused here by name, on either route, before anything
+        runs (a ventilated descriptor: by __init__ already)"""
+        eng = self.engine
+        if self.chemistry is not None:
+            raise NotImplementedError(
+                "parcel with coalescence: aqueous chemistry in the same run is not served")
+        check_collisions(collisions, counts)
+        if route == "fused" and eng.parcel_coal_library is None:
+            raise NotImplementedError(
+                f"engine `{eng.name}` has no library for the parcel with coalescence: "
+                "route='fused' is not available on it (route='stages' is)")
+
+    def _init_collisions(self, collisions, seed, terminal_velocity, dry_volume, kappa):
+        """the arrays of the third dynamic and its `sdm_step_cfg`: the identity permutation, all
+        rows live, kappa times dry volume, the counters of `CollisionRunner` per parcel, one
+        stream per parcel at position 0"""
+        eng, n_parcel, n_sd = self.engine, self.n_parcel, self.n_sd
+        self.coal_cfg, self._coal_law, self.coal_dt_range = collision_cfg(
+            eng, collisions, self.dt, float(self.formulae.constants.rho_w), terminal_velocity)
+        seeds = np.broadcast_to(np.asarray(collisions.seed if seed is None else seed),
+                                (n_parcel,))
+        words = np.array([abi.pcg64_state_inc(int(s)) for s in seeds], dtype=np.uint64)
+        self._seed_words = words
+        self.rng_state_inc = eng.upload(words.reshape(-1).view(np.int64).copy())
+        self.rng_offset = eng.zeros(n_parcel, INT)
+        self.idx = eng.upload(np.arange(n_sd, dtype=np.int64))
+        self.n_live = eng.upload(np.diff(self.parcel_start_host).astype(np.int64))
+        self.kappa_times_dry_volume = eng.upload(np.ascontiguousarray(kappa * dry_volume))
+        self.coal_counters = {name: eng.zeros(n_parcel, INT) for name in COAL_COUNTERS}
+        self.stats_n_substep = eng.full(n_parcel, INT,
+                                        0 if collisions.adaptive else collisions.substeps)
+        self.stats_dt_min = eng.full(n_parcel, FLOAT, np.nan)
+        self.coal_events = eng.zeros(n_parcel, INT)
+        self._fresh_idx = True
+
+    def _coal_columns(self, get=lambda array: array):
+        """the columns coalescence adds to a snapshot, by name (`get` applied to every array)"""
+        out = {"multiplicity": get(self.multiplicity), "dry_volume": get(self.dry_volume),
+               "kappa": get(self.kappa),
+               "kappa_times_dry_volume": get(self.kappa_times_dry_volume),
+               "idx": get(self.idx), "n_live": get(self.n_live),
+               "stats_n_substep": get(self.stats_n_substep),
+               "stats_dt_min": get(self.stats_dt_min), "events": get(self.coal_events),
+               "rng_offset": get(self.rng_offset)}
+        out.update({name: get(array) for name, array in self.coal_counters.items()})
+        return out
+
+    def _coal_record(self, n_rows):
+        eng = self.engine
+        return {name: eng.full(n_rows, FLOAT, np.nan) if name == "dv"
+                else eng.full(n_rows, INT, -1) for name in abi.PARCEL_COAL_PROFILE_FIELDS}
+
+    def _coal_call(self, record):
+        law = self._coal_law or {}
+        return {"cfg": self.coal_cfg, "idx": self.idx, "n_live": self.n_live,
+                "kappa_times_dry_volume": self.kappa_times_dry_volume, **self.coal_counters,
+                "stats_n_substep": self.stats_n_substep, "stats_dt_min": self.stats_dt_min,
+                "events": self.coal_events, "rng_offset": self.rng_offset,
+                "rng_state_inc": self.rng_state_inc, "gk_a": law.get("gk_a"),
+                "gk_b": law.get("gk_b"), "velocity_params": law.get("velocity_params"),
+                "fresh_idx": self._fresh_idx, "profile": record}
+
+    def _coal_warnings(self):
+        """the events of the last call as the warnings `CollisionRunner` issues"""
+        eng = self.engine
+        events = eng.download(self.coal_events)
+        if (events & abi.PARCEL_COAL_EVENT_BOUND).any():
+            eng.assign(self.coal_events, eng.upload(events & ~abi.PARCEL_COAL_EVENT_BOUND))
+            raise RuntimeError("parcel with coalescence: an adaptive time step did not end "
+                               "within the bound its own arithmetic sets, in parcels "
+                               f"{np.flatnonzero(events & abi.PARCEL_COAL_EVENT_BOUND).tolist()}")
+        overflows = events >> abi.PARCEL_COAL_OVERFLOW_SHIFT
+        if (events & abi.PARCEL_COAL_EVENT_DT_MIN).any():
+            # the reference's condition (collision.py:276-277; a NaN entry, the initial state,
+            # silences it)
+            if np.min(eng.download(self.stats_dt_min)) == self.coal_dt_range[0]:
+                warnings.warn("adaptive time-step reached dt_min")
+        if (overflows > 0).any() and self.collisions.warn_overflows:
+            warnings.warn("overflow")
+        if events.any():
+            eng.fill(self.coal_events, 0)
+
+    def _live_rows(self):
+        """(rows of every parcel's live positions in position order, their parcel_start)"""
+        idx = self.engine.download(self.idx)
+        n_live = self.engine.download(self.n_live)
+        starts = self.parcel_start_host
+        rows = np.concatenate([idx[starts[c]:starts[c] + n_live[c]]
+                               for c in range(self.n_parcel)])
+        return rows.astype(np.int64), np.concatenate(([0], np.cumsum(n_live))).astype(np.int64)
+
+    def _run_stages_coal(self, w_mid, record, coal_record):  # pylint: disable=too-many-locals,too-many-statements
+        """the time step of include/sdm_parcel_coal.h with the stage symbols, parcel after
+        parcel: the stage step of `_run_stages` over the parcel's slice with its permutation and
+        live count, `sdm_collision_step` with n_cell = 1 and the step's dv on that slice, the
+        division of point 3.  The yardstick of the fused route"""
+        eng, const, cfg, setup = self.engine, self.formulae.constants, self.cfg, self.setup
+        host = {name: eng.download(array) for name, array in self.state.items()}
+        rows = {name: (eng.download(array) if array is not None else None)
+                for name, array in (record or {}).items()}
+        coal_rows = {name: eng.download(array) for name, array in coal_record.items()}
+        idx_host, n_live = eng.download(self.idx), eng.download(self.n_live)
+        offsets, events = eng.download(self.rng_offset), eng.download(self.coal_events)
+        one = {name: eng.empty(1, FLOAT) for name in
+               ("rhod", "thd", "qv", "prhod", "pthd", "pqv", "T", "p", "RH", "RH_max", "lv")}
+        counters = {name: eng.empty(1, INT) for name in
+                    ("n_substeps", "n_activating", "n_deactivating", "n_ripening")}
+        success = eng.zeros(1, np.uint8)
+        zero = eng.zeros(1, INT)
+        most = int(np.diff(self.parcel_start_host).max())
+        v_wet, backup, v_cr = (eng.empty(most, FLOAT) for _ in range(3))
+        cell = eng.zeros(most, INT)
+        block, spare = eng.empty(3 * most, FLOAT), eng.empty(most, INT)
+        dt_left = eng.empty(1, FLOAT)
+        dt_range = (setup.dt_cond_range[0], min(setup.dt_cond_range[1], self.dt))
+        n_parcel = self.n_parcel
+        law = self._coal_law or {}
+        result = abi.StepResult()
+
+        def address(array):
+            return None if array is None else abi.c_ptr(
+                array.data_ptr() if hasattr(array, "data_ptr") else array.ctypes.data)
+
+        for c in range(n_parcel):
+            if host["failed_step"][c] >= 0:
+                continue
+            r0, r1 = (int(v) for v in self.parcel_start_host[c:c + 2])
+            n_rows = r1 - r0
+            mass = self.water_mass[r0:r1]
+            for k in range(w_mid.shape[0]):
+                live = int(n_live[c])
+                rel_host = (idx_host[r0:r0 + live] - r0).astype(np.int64)
+                rel = eng.upload(rel_host)
+                cell_start = eng.upload(np.array([0, live], dtype=np.int64))
+                T, p = float(host["T"][c]), float(host["p"][c])
+                rhod, thd, qv = (float(host[v][c]) for v in ("rhod", "thd", "qv"))
+                w, dt = float(w_mid[k, c]), self.dt
+                delta = float(host["qv_prev"][c]) - qv
+                qv_mid = qv - delta / 2
+                lv = self._latent_heat(T, one["lv"])
+                Rq = const.Rv / (1 / qv_mid + 1) + const.Rd / (1 + qv_mid)
+                cp = const.c_pv / (1 / qv_mid + 1) + const.c_pd / (1 + qv_mid)
+                rho = p / Rq / T
+                dql_dz = delta / w / dt
+                drho_dz = (cfg.g_std / T * rho * (Rq / cp - 1)
+                           - p * lv / cp / (T * T) * dql_dz) / Rq
+                z = float(host["z"][c]) + dt * w
+                prhod = rhod + dt * (w * drho_dz)
+                dv = float(host["mass_of_dry_air"][c]) / ((prhod + rhod) / 2)
+                for name, value in (("rhod", rhod), ("thd", thd), ("qv", qv), ("prhod", prhod),
+                                    ("pthd", thd), ("pqv", qv), ("T", T)):
+                    eng.fill(one[name], value)
+                eng.fill(counters["n_substeps"], int(host["n_substeps"][c]))
+                eng.call("sdm_volume_of_water_mass", v_wet[:n_rows], mass, n_rows,
+                         float(const.rho_w))
+                eng.assign(backup[:n_rows], mass)
+                # the critical volume of the live rows only (the others are not written)
+                critical_volume_call(eng, self.formulae, v_cr[:n_rows], self.kappa[r0:r1],
+                                     self.f_org[r0:r1], self.dry_volume[r0:r1], v_wet[:n_rows],
+                                     one["T"], cell[:n_rows], n_rows)
+                self.critical_volume[r0:r1][rel] = v_cr[:n_rows][rel]
+                condensation_call(
+                    eng, formulae=self.formulae, n_sd=n_rows, n_cell=1, cell_start=cell_start,
+                    water_mass=mass, v_cr=self.critical_volume[r0:r1],
+                    multiplicity=self.multiplicity[r0:r1], vdry=self.dry_volume[r0:r1],
+                    idx=rel, rhod=one["rhod"], thd=one["thd"],
+                    water_vapour_mixing_ratio=one["qv"], dv=dv, prhod=one["prhod"],
+                    pthd=one["pthd"], predicted_water_vapour_mixing_ratio=one["pqv"],
+                    kappa=self.kappa[r0:r1], f_org=self.f_org[r0:r1], rtol_x=setup.rtol_x,
+                    rtol_thd=setup.rtol_thd, timestep=dt, counters=counters, cell_order=zero,
+                    RH_max=one["RH_max"], success=success, reynolds_number=None,
+                    air_density=None, air_dynamic_viscosity=None, dt_range=dt_range,
+                    adaptive=setup.adaptive, fuse=setup.fuse, multiplier=setup.multiplier,
+                    RH_rtol=setup.RH_rtol, max_iters=setup.max_iters, general=self.general,
+                    descriptor=self.descriptor)
+                if not eng.download(success)[0]:
+                    eng.assign(mass, backup[:n_rows])
+                    host["failed_step"][c] = host["steps_done"][c]
+                    break
+                temperature_pressure_rh_call(eng, self.formulae, one["prhod"], one["pthd"],
+                                             one["pqv"], one["T"], one["p"], one["RH"], 1)
+                n_sub = int(eng.download(counters["n_substeps"])[0])
+                if setup.adaptive:  # dynamics/condensation.py:122-131
+                    n_sub = min(max(n_sub, int(cfg.n_clamp_lo)), int(cfg.n_clamp_hi))
+                host["qv_prev"][c] = qv
+                host["z"][c], host["rhod"][c] = z, prhod
+                host["thd"][c] = eng.download(one["pthd"])[0]
+                host["qv"][c] = eng.download(one["pqv"])[0]
+                for name in ("T", "p", "RH", "RH_max"):
+                    host[name][c] = eng.download(one[name])[0]
+                host["n_substeps"][c] = n_sub
+                for name in ("n_activating", "n_deactivating", "n_ripening"):
+                    host[name][c] = eng.download(counters[name])[0]
+                host["steps_done"][c] += 1
+                for name, row in rows.items():
+                    if row is not None:
+                        row[k * n_parcel + c] = host[name][c]
+                # ---- point 2: the parcel as one cell of sdm_collision_step -----------------------
+                at = k * n_parcel + c
+                new_live, n_collision_sub = live, 0
+                before = {name: int(eng.download(self.coal_counters[name][c:c + 1])[0])
+                          for name in ("coalescence_rate", "collision_rate_deficit")}
+                if n_rows >= 2:
+                    columns = (mass, self.dry_volume[r0:r1], self.kappa_times_dry_volume[r0:r1])
+                    for a, column in enumerate(columns):
+                        eng.assign(block[a * n_rows:(a + 1) * n_rows], column)
+                    perm = eng.upload(np.concatenate(
+                        [rel_host, np.full(n_rows - live, n_rows, dtype=np.int64)]))
+                    ctl = eng.upload(np.array([live, live, 1, 1, 0, 0, 0, 0], dtype=np.int64))
+                    step_cfg = abi.StepCfg.from_buffer_copy(self.coal_cfg)
+                    step_cfg.n_sd, step_cfg.dv = n_rows, dv
+                    step_cfg.rng_state_inc = (abi.c_u64 * 4)(*(int(v) for v in
+                                                               self._seed_words[c]))
+                    state = abi.StepState()
+                    for name, array in (
+                            ("idx", perm), ("tmp_idx", spare[:n_rows]),
+                            ("multiplicity", self.multiplicity[r0:r1]),
+                            ("attributes", block[:3 * n_rows]), ("cell_id", cell[:n_rows]),
+                            ("cell_idx", zero), ("cell_start", cell_start),
+                            ("dt_left", dt_left), ("stats_dt_min", self.stats_dt_min[c:c + 1]),
+                            ("stats_n_substep", self.stats_n_substep[c:c + 1]),
+                            ("collision_rate", self.coal_counters["collision_rate"][c:c + 1]),
+                            ("collision_rate_deficit",
+                             self.coal_counters["collision_rate_deficit"][c:c + 1]),
+                            ("coalescence_rate",
+                             self.coal_counters["coalescence_rate"][c:c + 1]),
+                            ("gk_a", law.get("gk_a")), ("gk_b", law.get("gk_b")),
+                            ("velocity_params", law.get("velocity_params")), ("ctl", ctl)):
+                        setattr(state, name, address(array))
+                    state.known_valid = -1
+                    state.rng_offset = int(offsets[c])
+                    eng.call("sdm_collision_step", step_cfg, state, result, 1 | 2)
+                    words = list(result.ctl)
+                    if int(words[7]) & 0xff:
+                        raise RuntimeError("libsdm_hip: device-side failure in the fused "
+                                           f"collision step: code {int(words[7]) & 0xff}")
+                    now = eng.download(spare[:n_rows] if result.idx_swapped else perm)
+                    new_live = int(result.valid_n_sd)
+                    n_collision_sub = int(result.n_substeps)
+                    idx_host[r0:r0 + new_live] = r0 + now[:new_live]
+                    for a, column in enumerate(columns):
+                        eng.assign(column, block[a * n_rows:(a + 1) * n_rows])
+                    offsets[c] = int(result.rng_offset)
+                    n_live[c] = new_live
+                    if int(words[7]) & 0x100:
+                        events[c] |= abi.PARCEL_COAL_EVENT_DT_MIN
+                    if int(words[4]) > 0:
+                        events[c] += int(words[4]) << abi.PARCEL_COAL_OVERFLOW_SHIFT
+                # ---- point 3 -------------------------------------------------------------------------
+                alive = eng.upload((idx_host[r0:r0 + new_live] - r0).astype(np.int64))
+                self.kappa[r0:r1][alive] = (self.kappa_times_dry_volume[r0:r1][alive]
+                                            / self.dry_volume[r0:r1][alive])
+                coal_rows["n_live"][at] = new_live
+                coal_rows["n_substeps"][at] = n_collision_sub
+                for name, was in before.items():
+                    coal_rows[name][at] = int(eng.download(
+                        self.coal_counters[name][c:c + 1])[0]) - was
+                coal_rows["dv"][at] = dv
+        for name, value in coal_rows.items():
+            eng.assign(coal_record[name], eng.upload(value))
+        for name, value in (("idx", idx_host), ("n_live", n_live), ("rng_offset", offsets),
+                            ("coal_events", events)):
+            eng.assign(getattr(self, name), eng.upload(value))
+        for name, array in self.state.items():
+            eng.assign(array, eng.upload(host[name]))
+        for name, row in rows.items():
+            if row is not None:
+                eng.assign(record[name], eng.upload(row))
 
     # ---- construction from a spectrum ---------------------------------------------------------
     @classmethod
@@ -548,11 +946,19 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
         step PySDM's mesh.dv is the step's mid-point volume, which `run` reports)"""
         table = self._table(products)
         diag = self._diag_arrays(table, self.n_parcel, dv=False)
-        diagnose_call(self.engine, self.formulae, table.c_struct(),
-                      parcel_start=self.parcel_start, water_mass=self.water_mass,
-                      multiplicity=self.multiplicity, dry_volume=self.dry_volume,
-                      kappa=self.kappa, f_org=self.f_org, T=self.state["T"], diag=diag,
-                      descriptor=self.descriptor, general=self.general)
+        columns = {"parcel_start": self.parcel_start, "water_mass": self.water_mass,
+                   "multiplicity": self.multiplicity, "dry_volume": self.dry_volume,
+                   "kappa": self.kappa, "f_org": self.f_org}
+        if self.collisions is not None:
+            # every parcel's live rows in position order, gathered (rows that died hold no drop)
+            rows, starts = self._live_rows()
+            rows = self.engine.upload(rows)
+            columns = {name: array if name == "parcel_start" else array[rows]
+                       for name, array in columns.items()}
+            columns["parcel_start"] = self.engine.upload(starts)
+        diagnose_call(self.engine, self.formulae, table.c_struct(), **columns,
+                      T=self.state["T"], diag=diag, descriptor=self.descriptor,
+                      general=self.general)
         rhod = self.engine.download(self.state["rhod"])
         if dv is None:
             dv = self.engine.download(self.state["mass_of_dry_air"]) / rhod
@@ -581,12 +987,20 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
             raise ValueError("n_steps must not be negative")
         eng, n_parcel = self.engine, self.n_parcel
         record = None
+        if self.collisions is not None and (isinstance(products, RequestTable) or len(products)):
+            raise NotImplementedError(
+                "parcel with coalescence: products at output times come from `run(k); "
+                "diagnose(products)` (the per-step request table is not part of "
+                "sdm_parcel_run_coal)")
         table = self._table(products) if isinstance(products, RequestTable) or len(products) \
             else None
         diag = None
         chem_record = None
         if n_steps > 0 and self.chemistry is not None:
             chem_record = self._chem_record(n_steps * n_parcel)
+        coal_record = None
+        if n_steps > 0 and self.collisions is not None:
+            coal_record = self._coal_record(n_steps * n_parcel)
         if n_steps > 0:
             w_mid = self.w_mid(n_steps)
             if table is not None:
@@ -607,10 +1021,15 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
                             descriptor=self.descriptor, general=self.general,
                             requests=None if table is None else table.c_struct(), diag=diag,
                             chem=None if self.chemistry is None else self._chem_call(chem_record),
-                            vent=self._vent_call() if self.ventilated else None)
+                            vent=self._vent_call() if self.ventilated else None,
+                            coal=None if self.collisions is None
+                            else self._coal_call(coal_record))
+            elif self.collisions is not None:
+                self._run_stages_coal(w_mid, record, coal_record)
             else:
                 self._run_stages(w_mid, record, table, diag, chem_record)
             self.n_steps += n_steps
+            self._fresh_idx = False
         out = None
         if record is not None:
             out = {name: eng.download(array).reshape(n_steps, n_parcel)
@@ -636,6 +1055,15 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
                         "aq_total": np.stack([get(a) for a in chem_record["aq_total"]]),
                         "n_flagged": get(chem_record["n_flagged"]), "dv": get(chem_record["dv"])}
             self.last_chem_profile = chem_out
+        coal_out = None
+        if self.collisions is not None:
+            if coal_record is None:
+                coal_record = {name: eng.empty(0, FLOAT if name == "dv" else INT)
+                               for name in abi.PARCEL_COAL_PROFILE_FIELDS}
+            coal_out = {name: eng.download(array).reshape(n_steps, n_parcel)
+                        for name, array in coal_record.items()}
+            self.last_coal_profile = coal_out
+            self._coal_warnings()
         failed = eng.download(self.state["failed_step"])
         for parcel in np.flatnonzero(failed >= 0):
             if int(parcel) not in self._reported:
@@ -645,6 +1073,8 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
                 raise RuntimeError("Condensation failed", int(parcel), int(failed[parcel]))
         if self.chemistry is not None:
             return (out, chem_out) if table is None else (out, chem_out, values)
+        if self.collisions is not None:
+            return out, coal_out
         return out if table is None else (out, values)
 
     # ---- ventilation (include/sdm_parcel_vent.h) ---------------------------------------------------
@@ -897,6 +1327,14 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
             out["out_of_table"] = down(self.out_of_table)
         if self.chemistry is not None:
             out.update(self._chem_columns(down))
+        if self.collisions is not None:
+            out.update(self._coal_columns(down))
+            # (positions past a parcel's live ones hold nothing that is defined)
+            position = np.arange(self.n_sd) - np.repeat(self.parcel_start_host[:-1],
+                                                        np.diff(self.parcel_start_host))
+            out["idx"] = np.where(position < np.repeat(out["n_live"],
+                                                       np.diff(self.parcel_start_host)),
+                                  out["idx"], -1)
         return out
 
     def _chem_columns(self, get=lambda array: array):
@@ -924,10 +1362,14 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
                                out_of_table=self.out_of_table)
             if self.chemistry is not None:
                 columns.update(self._chem_columns())
+            if self.collisions is not None:
+                columns.update(self._coal_columns())
+                if name in ("idx", "n_live"):
+                    self._fresh_idx = True
             target = columns.get(name, self.state.get(name))
             if target is None:
                 raise KeyError(name)
-            dtype = INT if name in _INT_FIELDS + CHEM_COUNTERS + ("out_of_table",) else \
+            dtype = INT if name in _INT_FIELDS + CHEM_COUNTERS + COAL_COUNTERS + _COAL_INTS else \
                 np.uint8 if name == "do_chemistry_flag" else FLOAT
             value = np.ascontiguousarray(np.broadcast_to(
                 np.asarray(value, dtype=dtype), (eng.size(target),)))

@@ -51,6 +51,7 @@ fused step hands the state back.
 import copy
 import ctypes
 import importlib
+import warnings
 
 import numpy as np
 
@@ -506,6 +507,32 @@ _PARCEL_VARS = {"z": "z", "rhod": "rhod", "thd": "thd", "qv": "water_vapour_mixi
                 "T": "T", "p": "p", "RH": "RH"}
 
 
+def _coalescence_asked_for(particulator):
+    """whether the dynamics are AmbientThermodynamics, Condensation, Coalescence in that order;
+    the same three in another order, a Breakup or a Collision are refused by name"""
+    names = list(particulator.dynamics)
+    if "Collision" not in names:  # (PySDM files Collision, Coalescence and Breakup under it)
+        return False
+    kind = type(particulator.dynamics["Collision"]).__name__
+    if isinstance(particulator.dynamics["Collision"], FusedCollision):
+        kind = type(particulator.dynamics["Collision"].inner).__name__
+    if kind != "Coalescence":
+        raise ValueError(f"run_parcel serves Coalescence as the third dynamic, not {kind} "
+                         "(breakup stays on particulator.run)")
+    if sorted(names) != ["AmbientThermodynamics", "Collision", "Condensation"]:
+        raise ValueError("run_parcel needs exactly the dynamics AmbientThermodynamics, "
+                         f"Condensation and Coalescence, not {sorted(names)}")
+    if names != ["AmbientThermodynamics", "Condensation", "Collision"]:
+        raise ValueError("run_parcel with Coalescence needs the order AmbientThermodynamics, "
+                         f"Condensation, Coalescence, not {names}")
+    if isinstance(particulator.dynamics["Collision"], FusedCollision):
+        raise ValueError("run_parcel with Coalescence takes PySDM's own dynamic, not "
+                         "fuse(Coalescence)")
+    if not particulator.dynamics["Collision"].enable:
+        raise ValueError("run_parcel needs Coalescence(enable=True)")
+    return True
+
+
 def run_parcel(particulator, steps, products=()):
     """`steps` time steps of a built `Particulator` whose environment is a `Parcel` and whose
     dynamics are exactly `AmbientThermodynamics` and `Condensation`, in ONE `sdm_parcel_run` on the
@@ -527,6 +554,15 @@ def run_parcel(particulator, steps, products=()):
     current "air density" and "air dynamic viscosity" are the carried pair, read and left as
     `Moist.sync` leaves them.  Not with AqueousChemistry.
 
+    And `AmbientThermodynamics`, `Condensation`, `Coalescence`, registered in that order
+    (`sdm_parcel_run_coal`, include/sdm_parcel_coal.h; PySDM files the third under "Collision"):
+    the dynamic is mapped by `setup_from_pysdm`, the law by `velocity_law_from_pysdm`; the
+    particulator's own permutation (any order, sanitized first), multiplicities, extensive
+    attributes (exactly "signed water mass", "dry volume", "kappa times dry volume"), the
+    dynamic's counters, `stats_*` and the position of its random stream are read and left as
+    `particulator.run(steps)` leaves them; the warnings of `Collision` are issued afterwards.  Any
+    other order, a `Breakup` or a `Collision` are refused by name; no `products` with it.
+
     Observers and PySDM's own product objects are NOT notified per step.  `products` (objects of
     pysdm_amd.products, which carry PySDM's names, arguments and units) are evaluated inside the
     kernel's step loop after every step (`sdm_parcel_run_diag`, include/sdm_parcel_diag.h).
@@ -541,8 +577,12 @@ def run_parcel(particulator, steps, products=()):
         raise ValueError(f"run_parcel needs a Parcel environment, not {type(env).__name__}")
     with_chem = list(particulator.dynamics) == ["AmbientThermodynamics", "Condensation",
                                                 "AqueousChemistry"]
-    if not with_chem and sorted(particulator.dynamics) != ["AmbientThermodynamics",
-                                                           "Condensation"]:
+    with_coal = _coalescence_asked_for(particulator)
+    if with_coal and len(products):
+        raise NotImplementedError("run_parcel with Coalescence: products at output times come "
+                                  "from the particulator's own products after the call")
+    if not with_chem and not with_coal and sorted(particulator.dynamics) != [
+            "AmbientThermodynamics", "Condensation"]:
         raise ValueError("run_parcel needs exactly the dynamics AmbientThermodynamics and "
                          f"Condensation, not {sorted(particulator.dynamics)}")
     if "a_w_ice" in env.variables:
@@ -557,6 +597,9 @@ def run_parcel(particulator, steps, products=()):
     _parcel.check_hydrostatics(formulae)
     descriptor = check_formulae(formulae)
     ventilated = descriptor.option[_parcel._VENT] != 0  # pylint: disable=protected-access
+    if ventilated and with_coal:
+        raise ValueError("run_parcel: Coalescence with a ventilation other than Neglect stays on "
+                         "particulator.run")
     if ventilated and with_chem:
         raise ValueError("run_parcel: AqueousChemistry with a ventilation other than Neglect "
                          "stays on particulator.run")
@@ -573,8 +616,12 @@ def run_parcel(particulator, steps, products=()):
 
     attrs = particulator.attributes
     idx = getattr(attrs, _PRIVATE + "idx")
+    if with_coal:
+        attrs.sanitize()
     n_sd = int(len(idx))
-    if n_sd != int(particulator.n_sd) or not np.array_equal(
+    if with_coal:  # any permutation of the live super-droplets; the columns keep their length
+        n_live, n_sd = n_sd, int(particulator.n_sd)
+    elif n_sd != int(particulator.n_sd) or not np.array_equal(
             eng.download(idx.data)[:n_sd], np.arange(n_sd)):
         raise ValueError("run_parcel needs every super-droplet valid and in row order")
     current, tmp = env._values["current"], env._tmp  # pylint: disable=protected-access
@@ -633,6 +680,42 @@ def run_parcel(particulator, steps, products=()):
             "mixing_ratios": ratios, "consts": _chem.constants_of(formulae),
             "dry_factor": float(aqueous.dry_molar_mass) / float(aqueous.dry_rho),
             "counters": chem_counters, "profile": None}
+    coal_call = None
+    if with_coal:  # include/sdm_parcel_coal.h: the particulator's own arrays
+        collision = particulator.dynamics["Collision"]
+        coal_setup = setup_from_pysdm(collision, formulae)
+        _parcel.check_collisions(coal_setup, [n_sd])
+        if eng.parcel_coal_library is None:
+            raise NotImplementedError(
+                f"engine `{eng.name}` has no library for the parcel with coalescence")
+        keys = list(attrs.get_extensive_attribute_keys())
+        wanted = ["signed water mass", "dry volume", "kappa times dry volume"]
+        if sorted(keys) != sorted(wanted):
+            raise ValueError(f"run_parcel with Coalescence needs exactly the extensive attributes "
+                             f"{wanted}, not {keys}")
+        stream = collision.rnd_opt_coll.rnd
+        if not hasattr(stream, "state_inc") or not hasattr(stream, "offset"):
+            raise NotImplementedError("run_parcel with Coalescence needs the random stream of a "
+                                      "backend of this package")
+        coal_cfg, coal_law, coal_dt_range = _parcel.collision_cfg(
+            eng, coal_setup, dt, float(formulae.constants.rho_w),
+            velocity_law_from_pysdm(formulae))
+        live_count = eng.upload(np.array([n_live], dtype=np.int64))
+        coal_events = eng.zeros(1, INT)
+        stream_offset = eng.upload(np.array([stream.offset], dtype=np.int64))
+        words = np.array(stream.state_inc, dtype=np.uint64)
+        coal_call = {
+            "cfg": coal_cfg, "idx": idx.data, "n_live": live_count,
+            "kappa_times_dry_volume": attrs["kappa times dry volume"].data,
+            "collision_rate": collision.collision_rate.data,
+            "collision_rate_deficit": collision.collision_rate_deficit.data,
+            "coalescence_rate": collision.coalescence_rate.data,
+            "stats_n_substep": collision.stats_n_substep.data,
+            "stats_dt_min": collision.stats_dt_min.data, "events": coal_events,
+            "rng_offset": stream_offset,
+            "rng_state_inc": eng.upload(words.view(np.int64).copy()),
+            **{name: (coal_law or {}).get(name) for name in ("gk_a", "gk_b", "velocity_params")},
+            "fresh_idx": True, "profile": None}
     vent = None
     if ventilated:  # include/sdm_parcel_vent.h: the law of the formulae, the environment's air
         from .terminal_velocity import make_law  # pylint: disable=import-outside-toplevel
@@ -646,7 +729,7 @@ def run_parcel(particulator, steps, products=()):
                 "air_dynamic_viscosity": current["air dynamic viscosity"].data,
                 "reynolds_number": eng.empty(n_sd, FLOAT), "out_of_table": out_of_table}
     _parcel.parcel_call(
-        eng, formulae, cfg, n_steps=steps, chem=chem_call, vent=vent,
+        eng, formulae, cfg, n_steps=steps, chem=chem_call, vent=vent, coal=coal_call,
         parcel_start=eng.upload(np.array([0, n_sd], dtype=np.int64)),
         water_mass=attrs["signed water mass"].data, multiplicity=attrs["multiplicity"].data,
         dry_volume=attrs["dry volume"].data, kappa=attrs["kappa"].data,
@@ -655,6 +738,17 @@ def run_parcel(particulator, steps, products=()):
         profile=record, descriptor=descriptor,
         requests=None if table is None else table.c_struct(), diag=diag)
     attrs.mark_updated("signed water mass")
+    if with_coal:  # what Collision.__call__ and sanitize() leave behind
+        n_live = int(eng.download(live_count)[0])
+        setattr(attrs, _PRIVATE + "valid_n_sd", n_live)
+        idx.length = idx.INT(n_live)
+        setattr(attrs, _PRIVATE + "sorted", False)
+        attrs.mark_updated("multiplicity")
+        for key in attrs.get_extensive_attribute_keys():
+            attrs.mark_updated(key)
+        stream.offset = int(eng.download(stream_offset)[0])
+        if collision.adaptive:
+            eng.fill(collision.dt_left.data, 0.0)
     if with_chem:
         for key in _chem.AQUEOUS:
             attrs.mark_updated(f"moles_{key}")
@@ -690,6 +784,14 @@ def run_parcel(particulator, steps, products=()):
         raise RuntimeError("Condensation failed")
     if with_chem:
         _chem.raise_if_counted([int(eng.download(c)[0]) for c in chem_counters])
+    if with_coal:
+        events = int(eng.download(coal_events)[0])
+        if events & abi.PARCEL_COAL_EVENT_BOUND:
+            raise RuntimeError("run_parcel with Coalescence: an adaptive time step did not end "
+                               "within the bound its own arithmetic sets")
+        if events & abi.PARCEL_COAL_EVENT_DT_MIN and float(
+                eng.download(collision.stats_dt_min.data)[0]) == coal_dt_range[0]:
+            warnings.warn("adaptive time-step reached dt_min")  # collision.py:276-277
     if table is None:
         return rows
     from .products import Rows  # pylint: disable=import-outside-toplevel

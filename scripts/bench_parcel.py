@@ -38,6 +38,14 @@ PruppacherAndRasmussen1979 and the Gunn-Kinzer table): the fused route (`sdm_par
 against the fused route with the ventilation Neglect (through k_parcel and through k_parcel_f) at
 1, 16, 256 and 1024 parcels, and against the ventilated stage route at 1 and 16.  Writes
 profiles/parcel_vent_timing.json with the ratios; no threshold.
+
+`python scripts/bench_parcel.py --coalescence` times the parcel with coalescence
+(include/sdm_parcel_coal.h; Coalescence(Geometric()), adaptive): 1024 parcels of 256 rows on the
+fused route (`sdm_parcel_run_coal`) against `sdm_parcel_run` with one step per launch at the same
+shape (what the collisions add), and against the stage route (the stage step, then
+`sdm_collision_step` with n_cell = 1, parcel by parcel) at the same shape; once with the haze of
+the other measurements (nothing coalesces) and once with drizzle-sized drops (pairs do).  Writes
+profiles/parcel_coal_timing.json with the ratios; no threshold.
 """
 import argparse
 import json
@@ -60,7 +68,7 @@ CHEM_MOLE_FRACTIONS = {"SO2": 0.2e-9, "O3": 50e-9, "H2O2": 0.5e-9, "CO2": 360e-6
                        "NH3": 0.1e-9}
 
 
-def make_runner(kind, n_parcel, route, steps_per_launch, engine=None, system=None):
+def make_runner(kind, n_parcel, route, steps_per_launch, engine=None, system=None, **more):
     from pysdm_amd import spectra  # pylint: disable=import-outside-toplevel
     from pysdm_amd.condensation import CondensationSetup  # pylint: disable=import-outside-toplevel
     from pysdm_amd.engine import HipEngine  # pylint: disable=import-outside-toplevel
@@ -80,7 +88,7 @@ def make_runner(kind, n_parcel, route, steps_per_launch, engine=None, system=Non
         p0=100000.0, qv0=0.012, w=updrafts, mass_of_dry_air=1.0,
         spectrum=spectra.Lognormal(norm_factor=60e6 / 1.18, m_mode=0.04e-6, s_geom=1.4),
         kappa=1.28, f_org=None if kind == "default" else 0.3, n_sd=N_SD, n_parcel=n_parcel,
-        route=route, steps_per_launch=steps_per_launch, **chemistry)
+        route=route, steps_per_launch=steps_per_launch, **chemistry, **more)
 
 
 def timed(runner, start, steps, reps, warmup, call=None):
@@ -321,6 +329,76 @@ def main_ventilation(args):
     print("wrote", out)
 
 
+COAL_PARCELS, COAL_STEPS = 1024, 20
+COAL_DRIZZLE_RADII = (10e-6, 50e-6)
+
+
+def measure_coalescence(mode, n_parcel, reps, warmup, spectrum="haze", engine=None):
+    """`mode`: "fused" (sdm_parcel_run_coal), "stages" (the stage step, then sdm_collision_step with
+    n_cell = 1, parcel by parcel) or "condensation only" (sdm_parcel_run, one step per launch).
+    `spectrum`: "haze" (the aerosol of the other measurements at equilibrium: the Geometric kernel
+    finds next to nothing to collect in 20 s, so a step is one sub-step of shuffle, pairing and
+    probabilities) or "drizzle" (the same rows with seeded radii of 10 - 50 micrometres: pairs
+    coalesce)"""
+    from pysdm_amd import recipe  # pylint: disable=import-outside-toplevel
+
+    more = {}
+    if mode != "condensation only":
+        more["collisions"] = recipe.CollisionSetup.coalescence(recipe.Geometric(), adaptive=True)
+    runner = make_runner("default", n_parcel, "stages" if mode == "stages" else "fused",
+                         1 if mode == "condensation only" else 0, engine=engine, **more)
+    if spectrum == "drizzle":
+        rng = np.random.default_rng(11)
+        radii = np.exp(rng.uniform(*np.log(COAL_DRIZZLE_RADII), runner.n_sd))
+        runner.restore({"water_mass": 1000.0 * 4 / 3 * np.pi * radii ** 3})
+    start = runner.snapshot()
+    samples = timed(runner, start, COAL_STEPS, reps, warmup)
+    final = runner.snapshot()
+    assert (final["failed_step"] == -1).all() and (final["steps_done"] == COAL_STEPS).all()
+    ms = float(np.median(samples))
+    out = {"mode": mode, "spectrum": spectrum, "n_parcel": n_parcel, "n_sd_per_parcel": N_SD,
+           "steps": COAL_STEPS,
+           "reps": reps, "ms_median": round(ms, 3), "ms_min": round(float(np.min(samples)), 3),
+           "ms_max": round(float(np.max(samples)), 3),
+           "ms_per_parcel_step": round(ms / (n_parcel * COAL_STEPS), 5)}
+    if mode != "condensation only":
+        out["collision_substeps_per_step"] = round(
+            float(runner.last_coal_profile["n_substeps"].mean()), 2)
+        out["coalescence_rate_total"] = int(final["coalescence_rate"].sum())
+        out["n_live_min"] = int(final["n_live"].min())
+    return out
+
+
+def main_coalescence(args):
+    results = []
+    for spectrum in ("haze", "drizzle"):
+        for mode in ("condensation only", "fused", "stages"):
+            # (the stage route: some 20 s per call at this shape; one call, no warm-up)
+            reps, warmup = (1, 0) if mode == "stages" else (args.reps, args.warmup)
+            results.append(measure_coalescence(mode, COAL_PARCELS, reps, warmup, spectrum))
+            print(json.dumps(results[-1]), flush=True)
+    by = {(r["mode"], r["spectrum"]): r["ms_median"] for r in results}
+    ratios = {
+        f"{spectrum}: {name}": round(by[top, spectrum] / by[bottom, spectrum], 3)
+        for spectrum in ("haze", "drizzle")
+        for name, top, bottom in (
+            ("fused with coalescence / condensation only", "fused", "condensation only"),
+            ("stages / fused", "stages", "fused"))}
+    out = args.out or os.path.join(ROOT, "profiles", "parcel_coal_timing.json")
+    with open(out, "w", encoding="utf-8") as handle:
+        handle.write(json.dumps({
+            "workload": f"{N_SD} super-droplets per parcel, {COAL_STEPS} steps of {DT} s, updrafts "
+                        "0.2 .. 5 m/s; PySDM's default formulae; Coalescence(Geometric()), "
+                        f"adaptive, Gunn-Kinzer table; {COAL_PARCELS} parcels on every route; "
+                        "spectrum haze: the aerosol at equilibrium (next to no coalescence: one "
+                        "sub-step of shuffle and probabilities per step), drizzle: seeded radii of "
+                        f"10 - 50 micrometres (pairs coalesce); HIP events, median of {args.reps} "
+                        f"after {args.warmup} warm-up call(s) (the stage route: one call)",
+            "results": results, "ratios": ratios}, indent=1) + "\n")
+    print(json.dumps(ratios))
+    print("wrote", out)
+
+
 def main():
     parser = argparse.ArgumentParser()
     parser.add_argument("--reps", type=int, default=5)
@@ -336,7 +414,12 @@ def main():
                         help="time the parcel with aqueous chemistry instead (see the docstring)")
     parser.add_argument("--ventilation", action="store_true",
                         help="time the ventilated parcel instead (see the docstring)")
+    parser.add_argument("--coalescence", action="store_true",
+                        help="time the parcel with coalescence instead (see the docstring)")
     args = parser.parse_args()
+    if args.coalescence:
+        main_coalescence(args)
+        return
     if args.ventilation:
         main_ventilation(args)
         return

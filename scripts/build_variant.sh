@@ -14,7 +14,7 @@ mkdir -p "$root/build_variants"
 FLAGS="-O3 -std=c++17 --offload-arch=gfx950 -fPIC -ffp-contract=off -fno-fast-math -Wno-unused-function"
 pids=()
 # (every translation unit of pysdm_amd/csrc/build.sh: the engine refuses a library that lacks one)
-for f in ctx index collisions fused displacement calib comm condensation condensation_formulae parcel parcel_chem freezing deposition chemistry seeding relaxed_velocity initialisation; do
+for f in ctx index collisions fused displacement calib comm condensation condensation_formulae parcel parcel_chem parcel_coal freezing deposition chemistry seeding relaxed_velocity initialisation; do
   extra=("$@")
   if [ -n "${ONLY:-}" ] && [ "$f" != "$ONLY" ]; then extra=(); fi
   /opt/rocm/bin/hipcc $FLAGS "${extra[@]}" -c "$root/pysdm_amd/csrc/$f.hip" -o "$tmp/$f.o" 2>"$tmp/$f.log" &
