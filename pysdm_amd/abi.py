@@ -49,6 +49,9 @@ PARCEL_CHEM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "sdm_p
 PARCEL_VENT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "sdm_parcel_vent.h")
 # and the parcel with coalescence (condensation and collisions in one call)
 PARCEL_COAL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "sdm_parcel_coal.h")
+# and the parcel with collisional breakup (Collision and Breakup in the same call)
+PARCEL_BREAKUP_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include",
+                                          "sdm_parcel_breakup.h")
 # SDM_HIP_LIB: another build of the same library (tuning variants); still no fallback
 HIP_LIB_PATH = os.environ.get("SDM_HIP_LIB") or os.path.join(_HERE, "libsdm_hip.so")
 
@@ -256,6 +259,19 @@ class ParcelCoalProfile(ctypes.Structure):  # == sdm_parcel_coal_profile
     _fields_ = [(name, c_ptr) for name in PARCEL_COAL_PROFILE_FIELDS]
 
 
+# include/sdm_parcel_breakup.h
+PARCEL_BREAKUP_STATE_FIELDS = ("breakup_rate", "breakup_rate_deficit", "rng_offset_breakup")
+PARCEL_BREAKUP_PROFILE_FIELDS = ("breakup_rate", "breakup_rate_deficit", "n_overflow")
+
+
+class ParcelBreakupState(ctypes.Structure):  # == sdm_parcel_breakup_state
+    _fields_ = [(name, c_ptr) for name in PARCEL_BREAKUP_STATE_FIELDS]
+
+
+class ParcelBreakupProfile(ctypes.Structure):  # == sdm_parcel_breakup_profile
+    _fields_ = [(name, c_ptr) for name in PARCEL_BREAKUP_PROFILE_FIELDS]
+
+
 class RelaxedVelocityCfg(ctypes.Structure):  # == sdm_relaxed_velocity_cfg
     _fields_ = [
         ("n_sd", c_i64), ("gk_table_len", c_i64), ("dt", c_f64), ("c", c_f64), ("rho_w", c_f64),
@@ -436,6 +452,7 @@ _parcel_diag_library = None
 _parcel_chem_library = None
 _parcel_vent_library = None
 _parcel_coal_library = None
+_parcel_breakup_library = None
 
 
 def hip_library():
@@ -561,6 +578,15 @@ def parcel_coal_library():
         _parcel_coal_library = Library(HIP_LIB_PATH, "the HIP kernels of pysdm_amd",
                                        header=PARCEL_COAL_HEADER_PATH)
     return _parcel_coal_library
+
+
+def parcel_breakup_library():
+    """libsdm_hip.so bound to include/sdm_parcel_breakup.h (same file, same contexts)"""
+    global _parcel_breakup_library  # pylint: disable=global-statement
+    if _parcel_breakup_library is None:
+        _parcel_breakup_library = Library(HIP_LIB_PATH, "the HIP kernels of pysdm_amd",
+                                          header=PARCEL_BREAKUP_HEADER_PATH)
+    return _parcel_breakup_library
 
 
 def pcg64_state_inc(seed):

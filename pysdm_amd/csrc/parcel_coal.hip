@@ -27,6 +27,10 @@
 // square-and-multiply, at most 64 rounds for the stream position, 12 for a lane's offset in the
 // cell).  The position advances by N + N / 2 per sub-step, as sdm_collision_step's does.
 //
+// Breakup (include/sdm_parcel_breakup.h, sdm_parcel_run_collision): the same kernel with
+// BREAKUP = true - see the comment above k_parcel_coal.  The breakup stream is the parcel's own
+// generator at rng_offset_breakup[c], one draw per pair slot, advanced by N / 2 per sub-step.
+//
 // 256 lanes: the flagship shape is 256 rows per parcel - one position per lane in the shuffle and
 // one pair per lane of two waves - and 14 KiB of LDS per workgroup, so that the 32-wave limit (8
 // workgroups per CU), not LDS, bounds residency; at the cap of 2048 rows a lane owns 8 positions
@@ -36,7 +40,9 @@
 
 #include "parcel_solver.h"
 #include "collision_pairs.h"
+#include "breakup_pairs.h"
 #include "../../include/sdm_parcel_coal.h"
+#include "../../include/sdm_parcel_breakup.h"
 
 #define PCO_CB 256
 #define PCO_ROW_BYTES 56  // int64 + 3 doubles + 5 int32 + 2 int16
@@ -61,7 +67,16 @@ struct ParcelCoalArgs {
   uint64_t *rng_offset;
   const uint64_t *rng_state_inc;
   sdm_parcel_coal_profile pr;
+  // breakup (include/sdm_parcel_breakup.h): read by the BREAKUP instantiations only
+  int64_t *breakup_rate, *breakup_rate_deficit;
+  uint64_t *rng_offset_breakup;
+  sdm_parcel_breakup_profile bpr;
 };
+
+// a colliding pair of a sub-step as the breakup branch lists it: 24 B, what the shuffle's tables
+// s0, s1 and head hold per PAIR of rows - they are dead once the walks are over
+struct PcoCollided { int32_t j, k; double g, u_b; };
+static_assert(sizeof(PcoCollided) == 24, "one record in the place of two rows of s0, s1, head");
 
 // the jump by `delta` draws of the LCG with increment `inc` as an affine map: state * m + p
 struct PcgAff { u128 m, p; };
@@ -79,7 +94,14 @@ __device__ __forceinline__ PcgAff pcg_affine(u128 inc, uint64_t delta) {
   return {acc_mult, acc_plus};
 }
 
-template <int KERNEL, bool CLOSED>
+// BREAKUP: the step of include/sdm_parcel_breakup.h with enable_breakup - a colliding pair bounces,
+// coalesces or breaks up.  The pair loop only LISTS the colliding pairs {j, k, gamma, u_b} in LDS
+// (the efficiencies and fragmentations are transcendental-heavy and colliding pairs are rare:
+// inlined PCO_MAXPAIR times into the unrolled loop they would cost every lane their registers), and
+// all lanes then stride over the list and resolve it densely - k_resolve_dense's idea inside one
+// workgroup.  The resolution restates fused.hip's resolve_collision<true> on the LDS copy.  The
+// instantiations sdm_parcel_run_coal launches are the BREAKUP = false ones, as they were.
+template <int KERNEL, bool CLOSED, bool BREAKUP>
 __global__ void __launch_bounds__(PCO_CB)
 k_parcel_coal(sdm_step_cfg cfg, FusedArgs A, ParcelCoalArgs a) {
   VELOCITY_LAW_PROMISE(CLOSED);
@@ -92,7 +114,9 @@ k_parcel_coal(sdm_step_cfg cfg, FusedArgs A, ParcelCoalArgs a) {
   int16_t *jown = (int16_t *)(head + R), *next = jown + R;
   __shared__ double red[PCO_CB / SDM_WAVE];
   __shared__ int s_died, s_valid, s_bad;
-  __shared__ unsigned long long s_cnt[3];
+  // [3 ..]: breakup_rate, breakup_rate_deficit, n_overflow of the step; the fill of the pair list
+  __shared__ unsigned long long s_cnt[BREAKUP ? 7 : 3];
+  PcoCollided *const list = (PcoCollided *)s0;  // [R / 2], BREAKUP only (see PcoCollided)
   const int tid = (int)threadIdx.x;
   const bool need_r = KERNEL == SDM_KERNEL_GEOMETRIC || KERNEL == SDM_KERNEL_PARAMETERIZED ||
                       KERNEL == SDM_KERNEL_SIMPLE_GEOMETRIC;
@@ -110,6 +134,7 @@ k_parcel_coal(sdm_step_cfg cfg, FusedArgs A, ParcelCoalArgs a) {
       s_bad = 0;
       s_valid = live0;
       s_cnt[0] = s_cnt[1] = s_cnt[2] = 0;
+      if constexpr (BREAKUP) s_cnt[3] = s_cnt[4] = s_cnt[5] = s_cnt[6] = 0;
     }
     for (int q = tid; q < N; q += PCO_CB) s_n[q] = -1;
     __syncthreads();
@@ -136,7 +161,8 @@ k_parcel_coal(sdm_step_cfg cfg, FusedArgs A, ParcelCoalArgs a) {
     double stats_min = a.stats_dt_min[c];
     int64_t event = 0, subs = 0;
     int64_t rate = 0, deficit = 0, coalesced = 0;  // this lane's share of the step's counts
-    uint64_t drawn = 0;
+    int64_t broken = 0, broken_deficit = 0, overflows = 0;  // (BREAKUP)
+    uint64_t drawn = 0, drawn_b = 0;
     int valid = live0;
     if (N >= 2) {
       const u128 inc = (((u128)a.rng_state_inc[4 * c + 2]) << 64) | a.rng_state_inc[4 * c + 3];
@@ -144,6 +170,12 @@ k_parcel_coal(sdm_step_cfg cfg, FusedArgs A, ParcelCoalArgs a) {
       {  // the stream at this parcel's position (uniform: every lane computes it)
         const PcgAff to_now = pcg_affine(inc, a.rng_offset[c]);
         base = base * to_now.m + to_now.p;
+      }
+      u128 base_b = 0;  // BREAKUP: the same generator at the position of the proc / frag stream
+      if constexpr (BREAKUP) {
+        const PcgAff to_now = pcg_affine(inc, a.rng_offset_breakup[c]);
+        base_b = ((((u128)a.rng_state_inc[4 * c]) << 64) | a.rng_state_inc[4 * c + 1]) * to_now.m +
+                 to_now.p;
       }
       const int P = N / 2;
       const PcgAff over_u01 = pcg_affine(inc, (uint64_t)N);        // u01 window -> `rand`
@@ -164,6 +196,9 @@ k_parcel_coal(sdm_step_cfg cfg, FusedArgs A, ParcelCoalArgs a) {
         // ---- shuffle_local (index_methods.py:32-43): events, then backward walks ------------------
         for (int li = tid; li < n; li += PCO_CB) {
           s0[li] = -1; s1[li] = -1; head[li] = -1;
+        }
+        if constexpr (BREAKUP) {  // (the last sub-step's list was read before its closing barrier)
+          if (tid == 0) s_cnt[6] = 0;
         }
         __syncthreads();
         {
@@ -272,9 +307,12 @@ k_parcel_coal(sdm_step_cfg cfg, FusedArgs A, ParcelCoalArgs a) {
           const u128 rand0 = base * over_u01.m + over_u01.p;
           const PcgAff to_me = pcg_affine(inc, (uint64_t)d0);
           u128 st = rand0 * to_me.m + to_me.p;
+          u128 sb = 0;  // one draw per pair slot: the efficiency decision and the fragmentation
+          if constexpr (BREAKUP) sb = base_b * to_me.m + to_me.p;
 #pragma unroll
           for (int r = 0; r < PCO_MAXPAIR; ++r) {
             st = st * pcg_mult() + inc;
+            if constexpr (BREAKUP) sb = sb * pcg_mult() + inc;
             if (!pvalid[r]) continue;
             const double u = pcg_output(st);
             double p = pprob[r];
@@ -293,10 +331,98 @@ k_parcel_coal(sdm_step_cfg cfg, FusedArgs A, ParcelCoalArgs a) {
             g = (double)gc;
             if (g == 0) continue;
             const int j = pj[r], k = pk[r];
+            if constexpr (BREAKUP) {  // listed; resolved below (at most n / 2 records: they fit)
+              const int at = (int)atomicAdd(&s_cnt[6], 1ull);
+              PcoCollided rec;
+              rec.j = j; rec.k = k; rec.g = g; rec.u_b = pcg_output(sb);
+              list[at] = rec;
+              continue;
+            }
             coalesced += (int64_t)(g * (double)nk);
             coalesce_pair(j, k, g, s_n, s_x, 3, R);  // (physics.h, on the LDS copy)
             if (s_n[j] == 0 || s_n[k] == 0) s_died = 1;  // flag_zero_multiplicity
           }
+        }
+        if constexpr (BREAKUP) {
+          // ---- bounce, coalescence or breakup of the listed pairs (collisions_methods.py:247-311;
+          // fused.hip: resolve_collision<true>, on the LDS copy).  The pairs of a sub-step are
+          // disjoint and the counters integer sums: the result does not depend on the list's order
+          __syncthreads();
+          const int n_coll = (int)s_cnt[6];  // <= n_pairs
+          const bool need_ru = cfg.ec != SDM_EC_CONST || cfg.frag == SDM_FRAG_STRAUB2010 ||
+                               cfg.frag == SDM_FRAG_LOWLIST1982;
+          for (int t = tid; t < n_coll; t += PCO_CB) {
+            const PcoCollided rec = list[t];
+            int j = rec.j, k = rec.k;
+            const int j_in = j, k_in = k;
+            const double g = rec.g, u_b = rec.u_b;
+            const int64_t nk = s_n[k];
+            double ec, fm;
+            {  // radius and velocity on demand: there is no mirror record in LDS
+              SD sj, sk;
+              sj.n = s_n[j]; sj.m = s_x[j]; sj.r = sj.u = 0.0;
+              sk.n = nk; sk.m = s_x[k]; sk.r = sk.u = 0.0;
+              if (need_ru) {
+                derive_ru(cfg, A, sj, j);
+                derive_ru(cfg, A, sk, k);
+              }
+              breakup_params(cfg, A, sj, sk, u_b, ec, fm);
+            }
+            if (u_b - (ec + (1 - ec) * cfg.eb_const) > 0) continue;  // bounce
+            if (u_b - ec < 0) {
+              coalesced += (int64_t)(g * (double)nk);
+              coalesce_pair(j, k, g, s_n, s_x, 3, R);
+            } else {
+              bool ovf = false;
+              const double *mass = s_x;  // (mass_attr = 0)
+              // break_up / break_up_while (collisions_methods.py:135-243)
+              double gamma_deficit = g;
+              if (!cfg.handle_all_breakups) {
+                double take_from_j, new_mult_k;
+                int64_t gamma_j_k;
+                compute_transfer_multiplicities(g, s_n[j], nk, mass[j], mass[k], fm,
+                                                cfg.max_multiplicity, take_from_j, new_mult_k,
+                                                gamma_j_k, ovf);
+                gamma_deficit = g - (double)gamma_j_k;
+                broken += gamma_j_k * nk;
+                if (gamma_deficit != 0) broken_deficit += (int64_t)(gamma_deficit * (double)nk);
+                apply_breakup_transfer(j, k, take_from_j, new_mult_k, s_n, s_x, 3, R);
+              } else {
+                // (bounded: every pass but the last takes at least 1 from gamma_deficit - the
+                // g_int == 0 exit of fused.hip, where the reference's loop would never end)
+                while (gamma_deficit > 0) {
+                  double take_from_j, new_mult_k, gamma_j_k;
+                  const int64_t mj = s_n[j], mk = s_n[k];
+                  if (mk == mj) {
+                    take_from_j = (double)mj;
+                    new_mult_k = (mass[j] + mass[k]) / fm * (double)mk;
+                    if (new_mult_k > (double)cfg.max_multiplicity) {
+                      broken_deficit += (int64_t)(gamma_deficit * (double)mk);
+                      ovf = true;
+                      break;
+                    }
+                    gamma_j_k = gamma_deficit;
+                  } else {
+                    if (mk > mj) { const int t2 = j; j = k; k = t2; }
+                    int64_t g_int;
+                    compute_transfer_multiplicities(gamma_deficit, s_n[j], s_n[k], mass[j],
+                                                    mass[k], fm, cfg.max_multiplicity, take_from_j,
+                                                    new_mult_k, g_int, ovf);
+                    gamma_j_k = (double)g_int;
+                    if (g_int == 0) break;
+                  }
+                  broken += (int64_t)(gamma_j_k * (double)s_n[k]);
+                  gamma_deficit -= gamma_j_k;
+                  apply_breakup_transfer(j, k, take_from_j, new_mult_k, s_n, s_x, 3, R);
+                }
+                broken_deficit += (int64_t)(gamma_deficit * (double)s_n[k]);
+              }
+              overflows += ovf ? 1 : 0;
+            }
+            if (s_n[j_in] == 0 || s_n[k_in] == 0) s_died = 1;  // flag_zero_multiplicity
+          }
+          base_b = base_b * over_rand.m + over_rand.p;
+          drawn_b += (uint64_t)P;
         }
         base = (base * over_u01.m + over_u01.p) * over_rand.m + over_rand.p;
         drawn += (uint64_t)(N + P);
@@ -347,6 +473,15 @@ k_parcel_coal(sdm_step_cfg cfg, FusedArgs A, ParcelCoalArgs a) {
         if (d) atomicAdd(&s_cnt[1], (unsigned long long)d);
         if (k) atomicAdd(&s_cnt[2], (unsigned long long)k);
       }
+      if constexpr (BREAKUP) {
+        const int64_t b = wave_sum_i64(broken), bd = wave_sum_i64(broken_deficit),
+                      o = wave_sum_i64(overflows);
+        if (lane_id() == 0) {
+          if (b) atomicAdd(&s_cnt[3], (unsigned long long)b);
+          if (bd) atomicAdd(&s_cnt[4], (unsigned long long)bd);
+          if (o) atomicAdd(&s_cnt[5], (unsigned long long)o);
+        }
+      }
     }
     __syncthreads();
     if (tid == 0) {
@@ -358,12 +493,23 @@ k_parcel_coal(sdm_step_cfg cfg, FusedArgs A, ParcelCoalArgs a) {
       a.stats_dt_min[c] = stats_min;
       if (event) a.events[c] |= event;
       a.rng_offset[c] += drawn;
+      if constexpr (BREAKUP) {
+        a.breakup_rate[c] += (int64_t)s_cnt[3];
+        a.breakup_rate_deficit[c] += (int64_t)s_cnt[4];
+        if (s_cnt[5]) a.events[c] += (int64_t)(s_cnt[5] << SDM_PARCEL_COAL_OVERFLOW_SHIFT);
+        a.rng_offset_breakup[c] += drawn_b;
+      }
       const int64_t at = a.at0 + c;
       if (a.pr.n_live) a.pr.n_live[at] = valid;
       if (a.pr.n_substeps) a.pr.n_substeps[at] = subs;
       if (a.pr.coalescence_rate) a.pr.coalescence_rate[at] = (int64_t)s_cnt[2];
       if (a.pr.collision_rate_deficit) a.pr.collision_rate_deficit[at] = (int64_t)s_cnt[1];
       if (a.pr.dv) a.pr.dv[at] = dv;
+      if constexpr (BREAKUP) {
+        if (a.bpr.breakup_rate) a.bpr.breakup_rate[at] = (int64_t)s_cnt[3];
+        if (a.bpr.breakup_rate_deficit) a.bpr.breakup_rate_deficit[at] = (int64_t)s_cnt[4];
+        if (a.bpr.n_overflow) a.bpr.n_overflow[at] = (int64_t)s_cnt[5];
+      }
     }
   }
 }
@@ -385,56 +531,65 @@ int reserve_dv(sdm_ctx *ctx, size_t bytes) {
   return SDM_OK;
 }
 
-template <int KERNEL, bool CLOSED>
+template <int KERNEL, bool CLOSED, bool BREAKUP>
 int launch_coal(sdm_ctx *ctx, unsigned grid, size_t lds, const sdm_step_cfg &cfg,
                 const FusedArgs &A, const ParcelCoalArgs &a) {
-  hipLaunchKernelGGL((k_parcel_coal<KERNEL, CLOSED>), dim3(grid), dim3(PCO_CB), lds, ctx->stream,
-                     cfg, A, a);
+  hipLaunchKernelGGL((k_parcel_coal<KERNEL, CLOSED, BREAKUP>), dim3(grid), dim3(PCO_CB), lds,
+                     ctx->stream, cfg, A, a);
   LAUNCH_CHECK();
   return SDM_OK;
 }
-template <int KERNEL, bool CLOSED>
+template <int KERNEL, bool CLOSED, bool BREAKUP>
 int allow_lds(size_t lds) {  // large dynamic LDS must be opted into, per kernel (the caller asks
                              // from 48 KiB on, below any limit a runtime may apply)
-  HIP_TRY(hipFuncSetAttribute((const void *)k_parcel_coal<KERNEL, CLOSED>,
+  HIP_TRY(hipFuncSetAttribute((const void *)k_parcel_coal<KERNEL, CLOSED, BREAKUP>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   return SDM_OK;
 }
 
-#define COAL_DISPATCH(FN, ...)                                                                  \
+#define COAL_DISPATCH(FN, B, ...)                                                               \
   ([&]() -> int {                                                                               \
     switch (kc.kernel * 2 + (closed ? 1 : 0)) {                                                 \
-      case SDM_KERNEL_GOLOVIN * 2: return FN<SDM_KERNEL_GOLOVIN, false>(__VA_ARGS__);           \
-      case SDM_KERNEL_GOLOVIN * 2 + 1: return FN<SDM_KERNEL_GOLOVIN, true>(__VA_ARGS__);        \
-      case SDM_KERNEL_GEOMETRIC * 2: return FN<SDM_KERNEL_GEOMETRIC, false>(__VA_ARGS__);       \
-      case SDM_KERNEL_GEOMETRIC * 2 + 1: return FN<SDM_KERNEL_GEOMETRIC, true>(__VA_ARGS__);    \
-      case SDM_KERNEL_CONSTANT * 2: return FN<SDM_KERNEL_CONSTANT, false>(__VA_ARGS__);         \
-      case SDM_KERNEL_CONSTANT * 2 + 1: return FN<SDM_KERNEL_CONSTANT, true>(__VA_ARGS__);      \
+      case SDM_KERNEL_GOLOVIN * 2:                                                              \
+        return FN<SDM_KERNEL_GOLOVIN, false, B>(__VA_ARGS__);                                   \
+      case SDM_KERNEL_GOLOVIN * 2 + 1:                                                          \
+        return FN<SDM_KERNEL_GOLOVIN, true, B>(__VA_ARGS__);                                    \
+      case SDM_KERNEL_GEOMETRIC * 2:                                                            \
+        return FN<SDM_KERNEL_GEOMETRIC, false, B>(__VA_ARGS__);                                 \
+      case SDM_KERNEL_GEOMETRIC * 2 + 1:                                                        \
+        return FN<SDM_KERNEL_GEOMETRIC, true, B>(__VA_ARGS__);                                  \
+      case SDM_KERNEL_CONSTANT * 2:                                                             \
+        return FN<SDM_KERNEL_CONSTANT, false, B>(__VA_ARGS__);                                  \
+      case SDM_KERNEL_CONSTANT * 2 + 1:                                                         \
+        return FN<SDM_KERNEL_CONSTANT, true, B>(__VA_ARGS__);                                   \
       case SDM_KERNEL_PARAMETERIZED * 2:                                                        \
-        return FN<SDM_KERNEL_PARAMETERIZED, false>(__VA_ARGS__);                                \
+        return FN<SDM_KERNEL_PARAMETERIZED, false, B>(__VA_ARGS__);                             \
       case SDM_KERNEL_PARAMETERIZED * 2 + 1:                                                    \
-        return FN<SDM_KERNEL_PARAMETERIZED, true>(__VA_ARGS__);                                 \
+        return FN<SDM_KERNEL_PARAMETERIZED, true, B>(__VA_ARGS__);                              \
       case SDM_KERNEL_SIMPLE_GEOMETRIC * 2:                                                     \
-        return FN<SDM_KERNEL_SIMPLE_GEOMETRIC, false>(__VA_ARGS__);                             \
+        return FN<SDM_KERNEL_SIMPLE_GEOMETRIC, false, B>(__VA_ARGS__);                          \
       case SDM_KERNEL_SIMPLE_GEOMETRIC * 2 + 1:                                                 \
-        return FN<SDM_KERNEL_SIMPLE_GEOMETRIC, true>(__VA_ARGS__);                              \
-      case SDM_KERNEL_LINEAR * 2: return FN<SDM_KERNEL_LINEAR, false>(__VA_ARGS__);             \
-      default: return FN<SDM_KERNEL_LINEAR, true>(__VA_ARGS__);                                 \
+        return FN<SDM_KERNEL_SIMPLE_GEOMETRIC, true, B>(__VA_ARGS__);                           \
+      case SDM_KERNEL_LINEAR * 2:                                                               \
+        return FN<SDM_KERNEL_LINEAR, false, B>(__VA_ARGS__);                                    \
+      default:                                                                                  \
+        return FN<SDM_KERNEL_LINEAR, true, B>(__VA_ARGS__);                                     \
     }                                                                                           \
   })()
 
 }  // namespace
 
-extern "C" int sdm_parcel_run_coal(
-    sdm_ctx *ctx, const sdm_parcel_cfg *cfg, const sdm_step_cfg *coal_cfg, int64_t n_steps,
-    int64_t n_parcel, int64_t n_sd, const int64_t *parcel_start, double *water_mass,
-    int64_t *multiplicity, double *vdry, double *kappa, const double *f_org, double *v_cr,
-    const sdm_parcel_state *state, const double *w_mid, const sdm_parcel_profile *profile,
-    const double consts[34], const sdm_cond_formulae *formulae, const sdm_parcel_coal_state *coal,
-    const sdm_parcel_coal_profile *coal_profile, int fresh_idx) {
-  ARG_TRY(ctx && coal_cfg && coal);
+// both entry points; `who` names the one that was called.  `breakup` / `breakup_profile` are read
+// only with coal_cfg->enable_breakup (include/sdm_parcel_breakup.h)
+static int parcel_run_collision(
+    const char *who, sdm_ctx *ctx, const sdm_parcel_cfg *cfg, const sdm_step_cfg *coal_cfg,
+    int64_t n_steps, int64_t n_parcel, int64_t n_sd, const int64_t *parcel_start,
+    double *water_mass, int64_t *multiplicity, double *vdry, double *kappa, const double *f_org,
+    double *v_cr, const sdm_parcel_state *state, const double *w_mid,
+    const sdm_parcel_profile *profile, const double consts[34], const sdm_cond_formulae *formulae,
+    const sdm_parcel_coal_state *coal, const sdm_parcel_coal_profile *coal_profile, int fresh_idx,
+    const sdm_parcel_breakup_state *breakup, const sdm_parcel_breakup_profile *breakup_profile) {
   // what this route does not serve
-  ARG_TRY(!coal_cfg->enable_breakup);
   ARG_TRY(!coal_cfg->optimized_random);
   ARG_TRY(coal_cfg->croupier_local);
   ARG_TRY(coal_cfg->velocity_source == SDM_VELOCITY_TERMINAL);
@@ -444,8 +599,19 @@ extern "C" int sdm_parcel_run_coal(
   ARG_TRY(law != SDM_VELOCITY_LAW_POWER_SERIES ||
           (coal_cfg->velocity_terms >= 0 && coal_cfg->velocity_terms <= SDM_VELOCITY_MAX_TERMS));
   ARG_TRY(coal_cfg->kernel >= SDM_KERNEL_GOLOVIN && coal_cfg->kernel <= SDM_KERNEL_LINEAR);
-  const bool kernel_needs_velocity = coal_cfg->kernel == SDM_KERNEL_GEOMETRIC ||
-                                     coal_cfg->kernel == SDM_KERNEL_PARAMETERIZED;
+  const bool with_breakup = coal_cfg->enable_breakup != 0;
+  if (with_breakup) {
+    ARG_TRY(coal_cfg->ec >= SDM_EC_CONST && coal_cfg->ec <= SDM_EC_LOWLIST1982);
+    ARG_TRY(coal_cfg->frag >= SDM_FRAG_ALWAYS_N && coal_cfg->frag <= SDM_FRAG_LOWLIST1982);
+    ARG_TRY(coal_cfg->max_multiplicity >= 1);
+  }
+  // (the set-up needs a fall velocity: the kernel does, or an efficiency / fragmentation that
+  // forms the pair's kinetic energy)
+  const bool kernel_needs_velocity =
+      coal_cfg->kernel == SDM_KERNEL_GEOMETRIC || coal_cfg->kernel == SDM_KERNEL_PARAMETERIZED ||
+      (with_breakup &&
+       (coal_cfg->ec == SDM_EC_STRAUB2010 || coal_cfg->ec == SDM_EC_LOWLIST1982 ||
+        coal_cfg->frag == SDM_FRAG_STRAUB2010 || coal_cfg->frag == SDM_FRAG_LOWLIST1982));
   ARG_TRY(law != SDM_VELOCITY_LAW_GUNN_KINZER || !kernel_needs_velocity ||
           (coal->gk_a && coal->gk_b && coal_cfg->gk_table_len > 0));
   ARG_TRY(law == SDM_VELOCITY_LAW_GUNN_KINZER || !kernel_needs_velocity ||
@@ -464,6 +630,8 @@ extern "C" int sdm_parcel_run_coal(
   ARG_TRY(coal->idx && coal->n_live && coal->kappa_times_dry_volume && coal->collision_rate &&
           coal->collision_rate_deficit && coal->coalescence_rate && coal->stats_n_substep &&
           coal->stats_dt_min && coal->events && coal->rng_offset && coal->rng_state_inc);
+  ARG_TRY(!with_breakup || (breakup && breakup->breakup_rate && breakup->breakup_rate_deficit &&
+                            breakup->rng_offset_breakup));
 
   // the parcels' sizes (sdm_parcel_prepare has checked that they are positive and lie in the columns)
   std::vector<int64_t> starts((size_t)n_parcel + 1);
@@ -483,23 +651,22 @@ extern "C" int sdm_parcel_run_coal(
   for (int64_t c = 0; c < n_parcel; ++c) {
     const int64_t row0 = starts[(size_t)c], rows = starts[(size_t)c + 1] - row0;
     if (rows > SDM_PARCEL_COAL_MAX_ROWS) {
-      sdm_set_error("sdm_parcel_run_coal: parcel %lld has %lld rows, more than "
-                    "SDM_PARCEL_COAL_MAX_ROWS = %d", (long long)c, (long long)rows,
-                    SDM_PARCEL_COAL_MAX_ROWS);
+      sdm_set_error("%s: parcel %lld has %lld rows, more than SDM_PARCEL_COAL_MAX_ROWS = %d", who,
+                    (long long)c, (long long)rows, SDM_PARCEL_COAL_MAX_ROWS);
       return SDM_E_ARG;
     }
     most = rows > most ? rows : most;
     if (!fresh_idx) continue;
     const int64_t n = live[(size_t)c];
     if (n < 1 || n > rows) {
-      sdm_set_error("sdm_parcel_run_coal: n_live[%lld] = %lld is outside 1 .. %lld", (long long)c,
+      sdm_set_error("%s: n_live[%lld] = %lld is outside 1 .. %lld", who, (long long)c,
                     (long long)n, (long long)rows);
       return SDM_E_ARG;
     }
     for (int64_t p = 0; p < n; ++p) {
       const int64_t row = perm[(size_t)(row0 + p)];
       if (row < row0 || row >= row0 + rows) {
-        sdm_set_error("sdm_parcel_run_coal: idx[%lld] = %lld is outside the rows of parcel %lld",
+        sdm_set_error("%s: idx[%lld] = %lld is outside the rows of parcel %lld", who,
                       (long long)(row0 + p), (long long)row, (long long)c);
         return SDM_E_ARG;
       }
@@ -552,9 +719,19 @@ extern "C" int sdm_parcel_run_coal(
   a.rng_state_inc = coal->rng_state_inc;
   if (coal_profile) a.pr = *coal_profile;
   else memset(&a.pr, 0, sizeof(a.pr));
+  a.breakup_rate = a.breakup_rate_deficit = nullptr;
+  a.rng_offset_breakup = nullptr;
+  memset(&a.bpr, 0, sizeof(a.bpr));
+  if (with_breakup) {
+    a.breakup_rate = breakup->breakup_rate;
+    a.breakup_rate_deficit = breakup->breakup_rate_deficit;
+    a.rng_offset_breakup = breakup->rng_offset_breakup;
+    if (breakup_profile) a.bpr = *breakup_profile;
+  }
   const size_t lds = (size_t)a.cap * PCO_ROW_BYTES;
   if (lds > 48 * 1024) {
-    const int allowed = COAL_DISPATCH(allow_lds, lds);
+    const int allowed = with_breakup ? COAL_DISPATCH(allow_lds, true, lds)
+                                     : COAL_DISPATCH(allow_lds, false, lds);
     if (allowed != SDM_OK) return allowed;
   }
   call.identity = coal->idx;  // the parcel kernels follow the caller's permutation
@@ -568,8 +745,39 @@ extern "C" int sdm_parcel_run_coal(
                  : sdm_parcel_launch_default_perm(ctx, call, coal->n_live, dv);
     if (launched != SDM_OK) return launched;
     a.at0 = step * n_parcel;
-    const int collided = COAL_DISPATCH(launch_coal, ctx, grid, lds, kc, A, a);
+    const int collided = with_breakup ? COAL_DISPATCH(launch_coal, true, ctx, grid, lds, kc, A, a)
+                                      : COAL_DISPATCH(launch_coal, false, ctx, grid, lds, kc, A, a);
     if (collided != SDM_OK) return collided;
   }
   return SDM_OK;
+}
+
+extern "C" int sdm_parcel_run_coal(
+    sdm_ctx *ctx, const sdm_parcel_cfg *cfg, const sdm_step_cfg *coal_cfg, int64_t n_steps,
+    int64_t n_parcel, int64_t n_sd, const int64_t *parcel_start, double *water_mass,
+    int64_t *multiplicity, double *vdry, double *kappa, const double *f_org, double *v_cr,
+    const sdm_parcel_state *state, const double *w_mid, const sdm_parcel_profile *profile,
+    const double consts[34], const sdm_cond_formulae *formulae, const sdm_parcel_coal_state *coal,
+    const sdm_parcel_coal_profile *coal_profile, int fresh_idx) {
+  ARG_TRY(ctx && coal_cfg && coal);
+  ARG_TRY(!coal_cfg->enable_breakup);  // (served by sdm_parcel_run_collision)
+  return parcel_run_collision("sdm_parcel_run_coal", ctx, cfg, coal_cfg, n_steps, n_parcel, n_sd,
+                              parcel_start, water_mass, multiplicity, vdry, kappa, f_org, v_cr,
+                              state, w_mid, profile, consts, formulae, coal, coal_profile,
+                              fresh_idx, nullptr, nullptr);
+}
+
+extern "C" int sdm_parcel_run_collision(
+    sdm_ctx *ctx, const sdm_parcel_cfg *cfg, const sdm_step_cfg *coal_cfg, int64_t n_steps,
+    int64_t n_parcel, int64_t n_sd, const int64_t *parcel_start, double *water_mass,
+    int64_t *multiplicity, double *vdry, double *kappa, const double *f_org, double *v_cr,
+    const sdm_parcel_state *state, const double *w_mid, const sdm_parcel_profile *profile,
+    const double consts[34], const sdm_cond_formulae *formulae, const sdm_parcel_coal_state *coal,
+    const sdm_parcel_coal_profile *coal_profile, int fresh_idx,
+    const sdm_parcel_breakup_state *breakup, const sdm_parcel_breakup_profile *breakup_profile) {
+  ARG_TRY(ctx && coal_cfg && coal);
+  return parcel_run_collision("sdm_parcel_run_collision", ctx, cfg, coal_cfg, n_steps, n_parcel,
+                              n_sd, parcel_start, water_mass, multiplicity, vdry, kappa, f_org,
+                              v_cr, state, w_mid, profile, consts, formulae, coal, coal_profile,
+                              fresh_idx, breakup, breakup_profile);
 }

@@ -47,6 +47,8 @@ class Engine:
     parcel_vent_library = None
     # likewise include/sdm_parcel_coal.h
     parcel_coal_library = None
+    # likewise include/sdm_parcel_breakup.h
+    parcel_breakup_library = None
     # whether the fused collision step of `library` can take the fall velocity from the
     # "relative fall momentum" row; an engine that cannot must refuse, not ignore the request
     fused_momentum_velocity = False
@@ -188,6 +190,14 @@ class Engine:
         self._before_call()
         self.parcel_coal_library.invoke(symbol, self.handle, args)
 
+    def call_parcel_breakup(self, symbol, *args):
+        """a symbol of include/sdm_parcel_breakup.h"""
+        if self.parcel_breakup_library is None:
+            raise NotImplementedError(
+                f"engine `{self.name}` has no library for the parcel with breakup")
+        self._before_call()
+        self.parcel_breakup_library.invoke(symbol, self.handle, args)
+
     def _before_call(self):
         pass
 
@@ -229,6 +239,7 @@ class HipEngine(Engine):
         self.parcel_chem_library = abi.parcel_chem_library()
         self.parcel_vent_library = abi.parcel_vent_library()
         self.parcel_coal_library = abi.parcel_coal_library()
+        self.parcel_breakup_library = abi.parcel_breakup_library()
         self.handle = abi.c_ptr()
         self.library.check(self.library.cdll.sdm_ctx_create(ctypes.byref(self.handle),
                                                             abi.c_int(device_index)))

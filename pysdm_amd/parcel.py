@@ -54,8 +54,9 @@ _VENT = OPTION_ORDER.index("ventilation")
 VENT_STATE = ("air_density", "air_dynamic_viscosity")  # what a ventilated parcel carries
 CHEM_COUNTERS = ("n_failed", "n_negative", "n_exceeded")
 COAL_COUNTERS = ("collision_rate", "collision_rate_deficit", "coalescence_rate")
+BREAKUP_COUNTERS = ("breakup_rate", "breakup_rate_deficit")
 _COAL_INTS = ("out_of_table", "multiplicity", "idx", "n_live", "stats_n_substep", "events",
-              "rng_offset")
+              "rng_offset", "rng_offset_breakup") + BREAKUP_COUNTERS
 _DIAG_LANES = 256  # the partials of the SUM of include/sdm_parcel_diag.h
 
 
@@ -124,7 +125,10 @@ def parcel_call(engine, formulae, cfg, *, n_steps, parcel_start, water_mass, mul
     `rng_state_inc` as int64 arrays holding the unsigned words; the fall-velocity members may be
     missing), `fresh_idx` (default True) and `profile` (None, or a dict by the member names of
     sdm_parcel_coal_profile; entries may be missing); `multiplicity`, `dry_volume` and `kappa`
-    are then written"""
+    are then written.  With `coal["breakup"]` the call is `sdm_parcel_run_collision`
+    (include/sdm_parcel_breakup.h): a dict of the engine arrays of sdm_parcel_breakup_state by
+    their member names (`rng_offset_breakup` as an int64 array) and `profile` (None, or a dict
+    by the member names of sdm_parcel_breakup_profile)"""
     if descriptor is None:
         descriptor = check_formulae(formulae)
     if vent is not None and chem is not None:
@@ -155,11 +159,16 @@ def parcel_call(engine, formulae, cfg, *, n_steps, parcel_start, water_mass, mul
         if requests is not None or chem is not None or vent is not None:
             raise NotImplementedError("parcel with coalescence: no request table, chemistry or "
                                       "ventilation in the same call")
-        engine.call_parcel_coal(
-            "sdm_parcel_run_coal", args[0], coal["cfg"], *args[1:],
-            _coal_state_struct(engine, coal, n_parcel, int(engine.size(water_mass))),
-            _coal_profile_struct(engine, coal.get("profile"), n_steps * n_parcel),
-            int(bool(coal.get("fresh_idx", True))))
+        coal_args = (args[0], coal["cfg"], *args[1:],
+                     _coal_state_struct(engine, coal, n_parcel, int(engine.size(water_mass))),
+                     _coal_profile_struct(engine, coal.get("profile"), n_steps * n_parcel),
+                     int(bool(coal.get("fresh_idx", True))))
+        if coal.get("breakup") is None:
+            engine.call_parcel_coal("sdm_parcel_run_coal", *coal_args)
+        else:
+            engine.call_parcel_breakup(
+                "sdm_parcel_run_collision", *coal_args,
+                *_breakup_structs(engine, coal["breakup"], n_parcel, n_steps * n_parcel))
         return
     if requests is None and chem is None and vent is None:
         engine.call_parcel("sdm_parcel_run", *args)
@@ -285,6 +294,27 @@ def _coal_profile_struct(engine, profile, n_rows):
     return out
 
 
+def _breakup_structs(engine, breakup, n_parcel, n_rows):
+    """(abi.ParcelBreakupState, abi.ParcelBreakupProfile or None) of a dict of engine arrays by
+    the member names, and `profile`"""
+    state = abi.ParcelBreakupState()
+    for name in abi.PARCEL_BREAKUP_STATE_FIELDS:
+        array = breakup.get(name)
+        if array is not None and engine.size(array) != n_parcel:
+            raise ValueError(f"parcel: breakup[{name!r}] must hold {n_parcel} values")
+        setattr(state, name, _address(array, INT))
+    profile = breakup.get("profile")
+    if profile is None:
+        return state, None
+    record = abi.ParcelBreakupProfile()
+    for name in abi.PARCEL_BREAKUP_PROFILE_FIELDS:
+        array = profile.get(name)
+        if array is not None and engine.size(array) != n_rows:
+            raise ValueError(f"parcel: a breakup profile member must hold {n_rows} values")
+        setattr(record, name, _address(array, INT))
+    return state, record
+
+
 def diag_sum(multiplicity, values):
     """the SUM of include/sdm_parcel_diag.h of multiplicity * values on the host, add for add"""
     terms = np.asarray(multiplicity).astype(float) * np.asarray(values, dtype=float)
@@ -332,12 +362,15 @@ def diagnose_call(engine, formulae, requests, *, parcel_start, water_mass, multi
         _diag_struct(engine, {k: v for k, v in diag.items() if k != "dv"}, sizes, n_parcel))
 
 
-def check_collisions(collisions, counts):
-    """what `sdm_parcel_run_coal` refuses of a `recipe.CollisionSetup` and of the parcels' sizes,
-    refused by name"""
-    if collisions.breakup:
+def check_collisions(collisions, counts, breakup=False):
+    """what `sdm_parcel_run_coal` - with `breakup`: `sdm_parcel_run_collision` - refuses of a
+    `recipe.CollisionSetup` and of the parcels' sizes, refused by name"""
+    if collisions.breakup and not breakup:
         raise NotImplementedError("parcel with coalescence: breakup is not served "
-                                  "(CollisionSetup.coalescence only)")
+                                  "(CollisionSetup.coalescence only) unless asked for with "
+                                  "breakup=True (include/sdm_parcel_breakup.h)")
+    if collisions.breakup and int(collisions.max_multiplicity) < 1:
+        raise ValueError("parcel with breakup: max_multiplicity < 1")
     if collisions.optimized_random:
         raise NotImplementedError("parcel with coalescence: optimized_random is not served")
     if collisions.croupier != "local":
@@ -367,13 +400,20 @@ def collision_cfg(engine, collisions, dt, rho_w, terminal_velocity=None):
     cfg.croupier_local = int(collisions.croupier == "local")
     cfg.optimized_random = int(collisions.optimized_random)
     cfg.enable_breakup = int(collisions.breakup)
+    cfg.handle_all_breakups = int(collisions.handle_all_breakups)
     cfg.kernel = desc.get("kernel", 0)
-    for name, width in (("kernel_param", 2), ("kernel_berry_params", 13)):
+    cfg.ec, cfg.frag = desc.get("ec", 0), desc.get("frag", 0)
+    # (the breakup members as CollisionRunner.step_cfg fills them: the stage route's yardstick)
+    for name, width in (("kernel_param", 2), ("kernel_berry_params", 13), ("ec_param", 2),
+                        ("frag_param", 2), ("berry_params", 13)):
         setattr(cfg, name, (abi.c_f64 * width)(*desc.get(name, (0.0,) * width)))
     cfg.kernel_berry_unit = desc.get("kernel_berry_unit", 1.0)
-    cfg.berry_unit = 1.0
-    cfg.frag_nfmax = -1.0
+    cfg.berry_unit = desc.get("berry_unit", 1.0)
+    cfg.eb_const = desc.get("eb_const", 0.0)
+    cfg.frag_vmin, cfg.frag_nfmax = desc.get("frag_vmin", 0.0), desc.get("frag_nfmax", -1.0)
     cfg.rho_w, cfg.sgm_w = rho_w, k.sgm_w
+    cfg.straub_consts = (abi.c_f64 * 6)(k.CM, k.STRAUB_E_D1, k.STRAUB_MU2, k.VEDDER_1987_A,
+                                        k.VEDDER_1987_b, k.PI)
     cfg.max_multiplicity = int(collisions.max_multiplicity)
     if desc["needs_gk"]:
         name = tv.law_name(terminal_velocity or "GunnKinzer1949")
@@ -402,14 +442,18 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
                  counts, multiplicity, water_mass, dry_volume, kappa, f_org=None, route="fused",
                  steps_per_launch=0, general=False, chemistry=None, mole_fractions=None,
                  dry_rho=None, dry_molar_mass=None, initial_moles=None, molar_mass=None,
-                 terminal_velocity=None, descriptor=None, collisions=None, seed=None):
+                 terminal_velocity=None, descriptor=None, collisions=None, seed=None,
+                 breakup=False):
         """`terminal_velocity`: a name or a law object of pysdm_amd.terminal_velocity, needed
         (and read) with a ventilation other than Neglect, and by the collision kernels that take
         a fall velocity (the Gunn-Kinzer table if not given).  `descriptor`: one of
         `condensation.descriptor_of` instead of the formulae's own (a ventilation a `Formulae`
         refuses travels so).  `collisions`: a `recipe.CollisionSetup` of coalescence as the third
         dynamic (include/sdm_parcel_coal.h); `seed`: an int, or one per parcel (default: the
-        setup's), each parcel drawing from its own NumPy-PCG64 stream"""
+        setup's), each parcel drawing from its own NumPy-PCG64 stream.  `breakup=True`: the
+        third dynamic is `Collision` / `Breakup` (include/sdm_parcel_breakup.h) - `collisions` may
+        then be a set-up with breakup (CollisionSetup.collision, .breakup_only; without the keyword
+        such a set-up is refused); a set-up of coalescence runs as it does without the keyword"""
         if route not in ROUTES:
             raise ValueError(f"route must be one of {ROUTES}, not {route!r}")
         check_hydrostatics(formulae)
@@ -455,6 +499,9 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
             if engine.chemistry_library is None:
                 raise NotImplementedError(f"engine `{engine.name}` has no chemistry library")
         self.collisions = collisions
+        self.breakup = bool(breakup)
+        if self.breakup and collisions is None:
+            raise ValueError("breakup=True needs collisions=")
         if collisions is not None:
             self._check_collisions(collisions, route, counts)
         self.route, self.general = route, bool(general)
@@ -584,10 +631,14 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
         if self.chemistry is not None:
             raise NotImplementedError(
                 "parcel with coalescence: aqueous chemistry in the same run is not served")
-        check_collisions(collisions, counts)
+        check_collisions(collisions, counts, self.breakup)
         if route == "fused" and eng.parcel_coal_library is None:
             raise NotImplementedError(
                 f"engine `{eng.name}` has no library for the parcel with coalescence: "
+                "route='fused' is not available on it (route='stages' is)")
+        if route == "fused" and self.breakup and eng.parcel_breakup_library is None:
+            raise NotImplementedError(
+                f"engine `{eng.name}` has no library for the parcel with breakup: "
                 "route='fused' is not available on it (route='stages' is)")
 
     def _init_collisions(self, collisions, seed, terminal_velocity, dry_volume, kappa):
@@ -612,6 +663,9 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
         self.stats_dt_min = eng.full(n_parcel, FLOAT, np.nan)
         self.coal_events = eng.zeros(n_parcel, INT)
         self._fresh_idx = True
+        if self.breakup:  # include/sdm_parcel_breakup.h: the proc / frag stream at position 0
+            self.breakup_counters = {name: eng.zeros(n_parcel, INT) for name in BREAKUP_COUNTERS}
+            self.rng_offset_breakup = eng.zeros(n_parcel, INT)
 
     def _coal_columns(self, get=lambda array: array):
         """the columns coalescence adds to a snapshot, by name (`get` applied to every array)"""
@@ -623,16 +677,37 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
                "stats_dt_min": get(self.stats_dt_min), "events": get(self.coal_events),
                "rng_offset": get(self.rng_offset)}
         out.update({name: get(array) for name, array in self.coal_counters.items()})
+        if self.breakup:
+            out.update({name: get(array) for name, array in self.breakup_counters.items()})
+            out["rng_offset_breakup"] = get(self.rng_offset_breakup)
         return out
 
+    @property
+    def with_breakup(self):
+        """the collisions are a set-up with breakup (asked for with breakup=True)"""
+        return self.breakup and bool(self.collisions.breakup)
+
     def _coal_record(self, n_rows):
+        """the record of the call: the members of sdm_parcel_coal_profile and, with breakup, of
+        sdm_parcel_breakup_profile (the two sets of names are disjoint)"""
         eng = self.engine
-        return {name: eng.full(n_rows, FLOAT, np.nan) if name == "dv"
-                else eng.full(n_rows, INT, -1) for name in abi.PARCEL_COAL_PROFILE_FIELDS}
+        out = {name: eng.full(n_rows, FLOAT, np.nan) if name == "dv"
+               else eng.full(n_rows, INT, -1) for name in abi.PARCEL_COAL_PROFILE_FIELDS}
+        if self.with_breakup:
+            out.update({name: eng.full(n_rows, INT, -1)
+                        for name in abi.PARCEL_BREAKUP_PROFILE_FIELDS})
+        return out
 
     def _coal_call(self, record):
         law = self._coal_law or {}
-        return {"cfg": self.coal_cfg, "idx": self.idx, "n_live": self.n_live,
+        breakup = None
+        if self.breakup:
+            breakup = {**self.breakup_counters, "rng_offset_breakup": self.rng_offset_breakup,
+                       "profile": ({name: record[name]
+                                    for name in abi.PARCEL_BREAKUP_PROFILE_FIELDS}
+                                   if self.with_breakup else None)}
+            record = {name: record[name] for name in abi.PARCEL_COAL_PROFILE_FIELDS}
+        return {"cfg": self.coal_cfg, "breakup": breakup, "idx": self.idx, "n_live": self.n_live,
                 "kappa_times_dry_volume": self.kappa_times_dry_volume, **self.coal_counters,
                 "stats_n_substep": self.stats_n_substep, "stats_dt_min": self.stats_dt_min,
                 "events": self.coal_events, "rng_offset": self.rng_offset,
@@ -673,7 +748,9 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
         """the time step of include/sdm_parcel_coal.h with the stage symbols, parcel after
         parcel: the stage step of `_run_stages` over the parcel's slice with its permutation and
         live count, `sdm_collision_step` with n_cell = 1 and the step's dv on that slice, the
-        division of point 3.  The yardstick of the fused route"""
+        division of point 3.  With a set-up with breakup (include/sdm_parcel_breakup.h) the
+        collision step gets the parcel's breakup counters and the position of its proc / frag
+        stream.  The yardstick of the fused route"""
         eng, const, cfg, setup = self.engine, self.formulae.constants, self.cfg, self.setup
         host = {name: eng.download(array) for name, array in self.state.items()}
         rows = {name: (eng.download(array) if array is not None else None)
@@ -681,6 +758,7 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
         coal_rows = {name: eng.download(array) for name, array in coal_record.items()}
         idx_host, n_live = eng.download(self.idx), eng.download(self.n_live)
         offsets, events = eng.download(self.rng_offset), eng.download(self.coal_events)
+        offsets_b = eng.download(self.rng_offset_breakup) if self.with_breakup else None
         one = {name: eng.empty(1, FLOAT) for name in
                ("rhod", "thd", "qv", "prhod", "pthd", "pqv", "T", "p", "RH", "RH_max", "lv")}
         counters = {name: eng.empty(1, INT) for name in
@@ -778,8 +856,13 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
                 # ---- point 2: the parcel as one cell of sdm_collision_step -----------------------
                 at = k * n_parcel + c
                 new_live, n_collision_sub = live, 0
-                before = {name: int(eng.download(self.coal_counters[name][c:c + 1])[0])
-                          for name in ("coalescence_rate", "collision_rate_deficit")}
+                tracked = {name: self.coal_counters[name]
+                           for name in ("coalescence_rate", "collision_rate_deficit")}
+                if self.with_breakup:
+                    tracked.update(self.breakup_counters)
+                    coal_rows["n_overflow"][at] = 0
+                before = {name: int(eng.download(array[c:c + 1])[0])
+                          for name, array in tracked.items()}
                 if n_rows >= 2:
                     columns = (mass, self.dry_volume[r0:r1], self.kappa_times_dry_volume[r0:r1])
                     for a, column in enumerate(columns):
@@ -809,6 +892,10 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
                         setattr(state, name, address(array))
                     state.known_valid = -1
                     state.rng_offset = int(offsets[c])
+                    if self.with_breakup:
+                        for name, array in self.breakup_counters.items():
+                            setattr(state, name, address(array[c:c + 1]))
+                        state.rng_offset_breakup = int(offsets_b[c])
                     eng.call("sdm_collision_step", step_cfg, state, result, 1 | 2)
                     words = list(result.ctl)
                     if int(words[7]) & 0xff:
@@ -821,6 +908,9 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
                     for a, column in enumerate(columns):
                         eng.assign(column, block[a * n_rows:(a + 1) * n_rows])
                     offsets[c] = int(result.rng_offset)
+                    if self.with_breakup:
+                        offsets_b[c] = int(result.rng_offset_breakup)
+                        coal_rows["n_overflow"][at] = int(words[4])
                     n_live[c] = new_live
                     if int(words[7]) & 0x100:
                         events[c] |= abi.PARCEL_COAL_EVENT_DT_MIN
@@ -833,14 +923,14 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
                 coal_rows["n_live"][at] = new_live
                 coal_rows["n_substeps"][at] = n_collision_sub
                 for name, was in before.items():
-                    coal_rows[name][at] = int(eng.download(
-                        self.coal_counters[name][c:c + 1])[0]) - was
+                    coal_rows[name][at] = int(eng.download(tracked[name][c:c + 1])[0]) - was
                 coal_rows["dv"][at] = dv
         for name, value in coal_rows.items():
             eng.assign(coal_record[name], eng.upload(value))
         for name, value in (("idx", idx_host), ("n_live", n_live), ("rng_offset", offsets),
-                            ("coal_events", events)):
-            eng.assign(getattr(self, name), eng.upload(value))
+                            ("coal_events", events), ("rng_offset_breakup", offsets_b)):
+            if value is not None:
+                eng.assign(getattr(self, name), eng.upload(value))
         for name, array in self.state.items():
             eng.assign(array, eng.upload(host[name]))
         for name, row in rows.items():
@@ -1059,7 +1149,9 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
         if self.collisions is not None:
             if coal_record is None:
                 coal_record = {name: eng.empty(0, FLOAT if name == "dv" else INT)
-                               for name in abi.PARCEL_COAL_PROFILE_FIELDS}
+                               for name in abi.PARCEL_COAL_PROFILE_FIELDS + (
+                                   abi.PARCEL_BREAKUP_PROFILE_FIELDS if self.with_breakup
+                                   else ())}
             coal_out = {name: eng.download(array).reshape(n_steps, n_parcel)
                         for name, array in coal_record.items()}
             self.last_coal_profile = coal_out

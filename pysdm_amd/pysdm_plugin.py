@@ -507,18 +507,19 @@ _PARCEL_VARS = {"z": "z", "rhod": "rhod", "thd": "thd", "qv": "water_vapour_mixi
                 "T": "T", "p": "p", "RH": "RH"}
 
 
-def _coalescence_asked_for(particulator):
+def _coalescence_asked_for(particulator, breakup=False):
     """whether the dynamics are AmbientThermodynamics, Condensation, Coalescence in that order;
-    the same three in another order, a Breakup or a Collision are refused by name"""
+    the same three in another order, a Breakup or a Collision are refused by name - unless
+    `breakup`, which serves all three kinds"""
     names = list(particulator.dynamics)
     if "Collision" not in names:  # (PySDM files Collision, Coalescence and Breakup under it)
         return False
     kind = type(particulator.dynamics["Collision"]).__name__
     if isinstance(particulator.dynamics["Collision"], FusedCollision):
         kind = type(particulator.dynamics["Collision"].inner).__name__
-    if kind != "Coalescence":
+    if kind != "Coalescence" and not (breakup and kind in ("Collision", "Breakup")):
         raise ValueError(f"run_parcel serves Coalescence as the third dynamic, not {kind} "
-                         "(breakup stays on particulator.run)")
+                         "(breakup stays on particulator.run unless asked for with breakup=True)")
     if sorted(names) != ["AmbientThermodynamics", "Collision", "Condensation"]:
         raise ValueError("run_parcel needs exactly the dynamics AmbientThermodynamics, "
                          f"Condensation and Coalescence, not {sorted(names)}")
@@ -533,7 +534,7 @@ def _coalescence_asked_for(particulator):
     return True
 
 
-def run_parcel(particulator, steps, products=()):
+def run_parcel(particulator, steps, products=(), breakup=False):
     """`steps` time steps of a built `Particulator` whose environment is a `Parcel` and whose
     dynamics are exactly `AmbientThermodynamics` and `Condensation`, in ONE `sdm_parcel_run` on the
     particulator's own arrays (include/sdm_parcel.h; anything else: ValueError).  It leaves the
@@ -563,6 +564,12 @@ def run_parcel(particulator, steps, products=()):
     `particulator.run(steps)` leaves them; the warnings of `Collision` are issued afterwards.  Any
     other order, a `Breakup` or a `Collision` are refused by name; no `products` with it.
 
+    With `breakup=True` the third dynamic may also be `Collision` or `Breakup`
+    (`sdm_parcel_run_collision`, include/sdm_parcel_breakup.h): the dynamic's `breakup_rate` and
+    `breakup_rate_deficit` and the positions of its `rnd_opt_proc` and `rnd_opt_frag` streams (one
+    position: the two generators share seed and position) are read and left as
+    `particulator.run(steps)` leaves them too, and "overflow" is warned about as `Collision` does.
+
     Observers and PySDM's own product objects are NOT notified per step.  `products` (objects of
     pysdm_amd.products, which carry PySDM's names, arguments and units) are evaluated inside the
     kernel's step loop after every step (`sdm_parcel_run_diag`, include/sdm_parcel_diag.h).
@@ -577,7 +584,7 @@ def run_parcel(particulator, steps, products=()):
         raise ValueError(f"run_parcel needs a Parcel environment, not {type(env).__name__}")
     with_chem = list(particulator.dynamics) == ["AmbientThermodynamics", "Condensation",
                                                 "AqueousChemistry"]
-    with_coal = _coalescence_asked_for(particulator)
+    with_coal = _coalescence_asked_for(particulator, breakup)
     if with_coal and len(products):
         raise NotImplementedError("run_parcel with Coalescence: products at output times come "
                                   "from the particulator's own products after the call")
@@ -684,10 +691,13 @@ def run_parcel(particulator, steps, products=()):
     if with_coal:  # include/sdm_parcel_coal.h: the particulator's own arrays
         collision = particulator.dynamics["Collision"]
         coal_setup = setup_from_pysdm(collision, formulae)
-        _parcel.check_collisions(coal_setup, [n_sd])
+        _parcel.check_collisions(coal_setup, [n_sd], breakup)
         if eng.parcel_coal_library is None:
             raise NotImplementedError(
                 f"engine `{eng.name}` has no library for the parcel with coalescence")
+        if breakup and eng.parcel_breakup_library is None:
+            raise NotImplementedError(
+                f"engine `{eng.name}` has no library for the parcel with breakup")
         keys = list(attrs.get_extensive_attribute_keys())
         wanted = ["signed water mass", "dry volume", "kappa times dry volume"]
         if sorted(keys) != sorted(wanted):
@@ -716,6 +726,22 @@ def run_parcel(particulator, steps, products=()):
             "rng_state_inc": eng.upload(words.view(np.int64).copy()),
             **{name: (coal_law or {}).get(name) for name in ("gk_a", "gk_b", "velocity_params")},
             "fresh_idx": True, "profile": None}
+        if breakup and coal_setup.breakup:  # include/sdm_parcel_breakup.h
+            streams_b = (collision.rnd_opt_proc.rnd, collision.rnd_opt_frag.rnd)
+            if any(not hasattr(s, "state_inc") or not hasattr(s, "offset") for s in streams_b):
+                raise NotImplementedError("run_parcel with breakup needs the random streams of a "
+                                          "backend of this package")
+            if (streams_b[0].offset != streams_b[1].offset
+                    or any(tuple(s.state_inc) != tuple(stream.state_inc) for s in streams_b)):
+                raise ValueError("run_parcel with breakup: the streams of rnd_opt_proc and "
+                                 "rnd_opt_frag must share seed and position")
+            stream_offset_b = eng.upload(np.array([streams_b[0].offset], dtype=np.int64))
+            coal_call["breakup"] = {"breakup_rate": collision.breakup_rate.data,
+                                    "breakup_rate_deficit": collision.breakup_rate_deficit.data,
+                                    "rng_offset_breakup": stream_offset_b, "profile": None}
+        elif breakup:
+            coal_call["breakup"] = {"profile": None}
+            streams_b = ()
     vent = None
     if ventilated:  # include/sdm_parcel_vent.h: the law of the formulae, the environment's air
         from .terminal_velocity import make_law  # pylint: disable=import-outside-toplevel
@@ -747,6 +773,8 @@ def run_parcel(particulator, steps, products=()):
         for key in attrs.get_extensive_attribute_keys():
             attrs.mark_updated(key)
         stream.offset = int(eng.download(stream_offset)[0])
+        for stream_b in (streams_b if breakup else ()):
+            stream_b.offset = int(eng.download(stream_offset_b)[0])
         if collision.adaptive:
             eng.fill(collision.dt_left.data, 0.0)
     if with_chem:
@@ -792,6 +820,8 @@ def run_parcel(particulator, steps, products=()):
         if events & abi.PARCEL_COAL_EVENT_DT_MIN and float(
                 eng.download(collision.stats_dt_min.data)[0]) == coal_dt_range[0]:
             warnings.warn("adaptive time-step reached dt_min")  # collision.py:276-277
+        if events >> abi.PARCEL_COAL_OVERFLOW_SHIFT and coal_setup.warn_overflows:
+            warnings.warn("overflow")  # (as the reference's backend does with warn_overflows)
     if table is None:
         return rows
     from .products import Rows  # pylint: disable=import-outside-toplevel

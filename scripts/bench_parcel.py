@@ -46,6 +46,14 @@ shape (what the collisions add), and against the stage route (the stage step, th
 `sdm_collision_step` with n_cell = 1, parcel by parcel) at the same shape; once with the haze of
 the other measurements (nothing coalesces) and once with drizzle-sized drops (pairs do).  Writes
 profiles/parcel_coal_timing.json with the ratios; no threshold.
+
+`python scripts/bench_parcel.py --breakup` times the parcel with collisional breakup
+(include/sdm_parcel_breakup.h; Collision(Geometric(), ConstEc(0.5), ConstEb(1), Straub2010Nf),
+adaptive): 1024 parcels of 256 rows of drizzle-sized drops, in which pairs coalesce and break up,
+on the fused route (`sdm_parcel_run_collision`) against the stage route (the stage step, then
+`sdm_collision_step` with breakup, parcel by parcel) and against the same ascents with
+coalescence only.  Writes profiles/parcel_breakup_timing.json with the ratios; the one claim is
+that fused is not slower than stages.
 """
 import argparse
 import json
@@ -399,6 +407,80 @@ def main_coalescence(args):
     print("wrote", out)
 
 
+BREAKUP_STEPS = 10
+
+
+def breakup_collisions():
+    """the set-up of --breakup: half of the colliding pairs coalesce, the others break up into
+    Straub's fragments (at most 10 of them, none below a radius of 5 micrometres)"""
+    from pysdm_amd import recipe  # pylint: disable=import-outside-toplevel
+
+    return recipe.CollisionSetup.collision(
+        recipe.Geometric(), recipe.ConstEc(0.5), recipe.ConstEb(1.0),
+        recipe.Straub2010Nf(vmin=4 / 3 * np.pi * 5e-6 ** 3, nfmax=10), adaptive=True)
+
+
+def measure_breakup(mode, n_parcel, reps, warmup, engine=None, time_it=timed):
+    """`mode`: "fused" (sdm_parcel_run_collision), "stages" (the stage step, then
+    sdm_collision_step with n_cell = 1 and breakup, parcel by parcel) or "coalescence only"
+    (sdm_parcel_run_coal on the same drops)"""
+    from pysdm_amd import recipe  # pylint: disable=import-outside-toplevel
+
+    breakup = mode != "coalescence only"
+    collisions = breakup_collisions() if breakup else recipe.CollisionSetup.coalescence(
+        recipe.Geometric(), adaptive=True)
+    runner = make_runner("default", n_parcel, "stages" if mode == "stages" else "fused", 0,
+                         engine=engine, collisions=collisions, breakup=breakup)
+    rng = np.random.default_rng(11)
+    radii = np.exp(rng.uniform(*np.log(COAL_DRIZZLE_RADII), runner.n_sd))
+    runner.restore({"water_mass": 1000.0 * 4 / 3 * np.pi * radii ** 3})
+    start = runner.snapshot()
+    samples = time_it(runner, start, BREAKUP_STEPS, reps, warmup)
+    final = runner.snapshot()
+    assert (final["failed_step"] == -1).all() and (final["steps_done"] == BREAKUP_STEPS).all()
+    ms = float(np.median(samples))
+    out = {"mode": mode, "n_parcel": n_parcel, "n_sd_per_parcel": N_SD, "steps": BREAKUP_STEPS,
+           "reps": reps, "ms_median": round(ms, 3), "ms_min": round(float(np.min(samples)), 3),
+           "ms_max": round(float(np.max(samples)), 3),
+           "ms_per_parcel_step": round(ms / (n_parcel * BREAKUP_STEPS), 5),
+           "collision_substeps_per_step": round(
+               float(runner.last_coal_profile["n_substeps"].mean()), 2),
+           "coalescence_rate_total": int(final["coalescence_rate"].sum()),
+           "n_live_min": int(final["n_live"].min())}
+    if breakup:
+        assert final["breakup_rate"].sum() > 0  # a set-up in which breakups happen
+        out["breakup_rate_total"] = int(final["breakup_rate"].sum())
+        out["breakup_rate_deficit_total"] = int(final["breakup_rate_deficit"].sum())
+        out["n_overflow_total"] = int(runner.last_coal_profile["n_overflow"].sum())
+    return out
+
+
+def main_breakup(args):
+    results = []
+    for mode in ("coalescence only", "fused", "stages"):
+        # (the stage route: seconds per call at this shape; one call, no warm-up)
+        reps, warmup = (1, 0) if mode == "stages" else (args.reps, args.warmup)
+        results.append(measure_breakup(mode, COAL_PARCELS, reps, warmup))
+        print(json.dumps(results[-1]), flush=True)
+    by = {r["mode"]: r["ms_median"] for r in results}
+    ratios = {"stages / fused": round(by["stages"] / by["fused"], 3),
+              "fused with breakup / fused with coalescence only":
+                  round(by["fused"] / by["coalescence only"], 3)}
+    assert by["fused"] <= by["stages"], "the fused route is slower than the stage route"
+    out = args.out or os.path.join(ROOT, "profiles", "parcel_breakup_timing.json")
+    with open(out, "w", encoding="utf-8") as handle:
+        handle.write(json.dumps({
+            "workload": f"{N_SD} super-droplets per parcel, {BREAKUP_STEPS} steps of {DT} s, "
+                        "updrafts 0.2 .. 5 m/s; PySDM's default formulae; seeded radii of 10 - 50 "
+                        "micrometres; Collision(Geometric(), ConstEc(0.5), ConstEb(1), "
+                        "Straub2010Nf(vmin: r = 5 um, nfmax = 10)), adaptive, Gunn-Kinzer table; "
+                        f"{COAL_PARCELS} parcels on every route; HIP events, median of {args.reps} "
+                        f"after {args.warmup} warm-up call(s) (the stage route: one call)",
+            "results": results, "ratios": ratios}, indent=1) + "\n")
+    print(json.dumps(ratios))
+    print("wrote", out)
+
+
 def main():
     parser = argparse.ArgumentParser()
     parser.add_argument("--reps", type=int, default=5)
@@ -416,7 +498,12 @@ def main():
                         help="time the ventilated parcel instead (see the docstring)")
     parser.add_argument("--coalescence", action="store_true",
                         help="time the parcel with coalescence instead (see the docstring)")
+    parser.add_argument("--breakup", action="store_true",
+                        help="time the parcel with collisional breakup instead (see the docstring)")
     args = parser.parse_args()
+    if args.breakup:
+        main_breakup(args)
+        return
     if args.coalescence:
         main_coalescence(args)
         return
