@@ -52,6 +52,8 @@ PARCEL_COAL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "sdm_p
 # and the parcel with collisional breakup (Collision and Breakup in the same call)
 PARCEL_BREAKUP_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include",
                                           "sdm_parcel_breakup.h")
+# and the mixed-phase parcel (freezing and vapour deposition on ice inside the step loop)
+PARCEL_ICE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "sdm_parcel_ice.h")
 # SDM_HIP_LIB: another build of the same library (tuning variants); still no fallback
 HIP_LIB_PATH = os.environ.get("SDM_HIP_LIB") or os.path.join(_HERE, "libsdm_hip.so")
 
@@ -238,6 +240,29 @@ class ParcelVent(ctypes.Structure):  # == sdm_parcel_vent (include/sdm_parcel_ve
         ("gk_factor", c_f64), ("gk_top", c_f64), ("air_density", c_ptr),
         ("air_dynamic_viscosity", c_ptr), ("reynolds_number", c_ptr), ("out_of_table", c_ptr),
     ]
+
+
+# include/sdm_parcel_ice.h: SDM_PARCEL_ICE_*
+PARCEL_ICE_ORDERS = {"freezing_first": 0, "deposition_first": 1}
+PARCEL_ICE_STATE_FIELDS = ("a_w_ice", "RH_ice", "rng_offset", "rng_state_inc", "n_exceeded",
+                           "freezing_temperature", "immersed_surface_area",
+                           "temperature_of_last_freezing")
+PARCEL_ICE_PROFILE_FIELDS = ("a_w_ice", "RH_ice", "n_ice", "ice_mass", "n_exceeded", "dv")
+
+
+class ParcelIceCfg(ctypes.Structure):  # == sdm_parcel_ice_cfg (include/sdm_parcel_ice.h)
+    _fields_ = [(name, ctypes.c_int32) for name in (
+        "freezing", "deposition", "order", "singular", "immersion_freezing",
+        "homogeneous_freezing", "thaw", "j_het", "j_hom", "coordinate", "capacity", "kinetics",
+        "sum", "reserved")]
+
+
+class ParcelIceState(ctypes.Structure):  # == sdm_parcel_ice_state
+    _fields_ = [(name, c_ptr) for name in PARCEL_ICE_STATE_FIELDS]
+
+
+class ParcelIceProfile(ctypes.Structure):  # == sdm_parcel_ice_profile
+    _fields_ = [(name, c_ptr) for name in PARCEL_ICE_PROFILE_FIELDS]
 
 
 # include/sdm_parcel_coal.h: SDM_PARCEL_COAL_*
@@ -453,6 +478,7 @@ _parcel_chem_library = None
 _parcel_vent_library = None
 _parcel_coal_library = None
 _parcel_breakup_library = None
+_parcel_ice_library = None
 
 
 def hip_library():
@@ -569,6 +595,15 @@ def parcel_vent_library():
         _parcel_vent_library = Library(HIP_LIB_PATH, "the HIP kernels of pysdm_amd",
                                        header=PARCEL_VENT_HEADER_PATH)
     return _parcel_vent_library
+
+
+def parcel_ice_library():
+    """libsdm_hip.so bound to include/sdm_parcel_ice.h (same file, same contexts)"""
+    global _parcel_ice_library  # pylint: disable=global-statement
+    if _parcel_ice_library is None:
+        _parcel_ice_library = Library(HIP_LIB_PATH, "the HIP kernels of pysdm_amd",
+                                      header=PARCEL_ICE_HEADER_PATH)
+    return _parcel_ice_library
 
 
 def parcel_coal_library():

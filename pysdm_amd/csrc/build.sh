@@ -13,7 +13,7 @@ pids=()
 for f in ctx index collisions fused displacement calib comm condensation condensation_formulae parcel parcel_chem parcel_coal freezing deposition chemistry seeding relaxed_velocity initialisation; do
   stale=0
   [ -f $f.o ] || stale=1
-  for dep in $f.hip common.h sdm_math.h sdm_math_tables.h physics.h index.h shuffle_device.h shuffle_build.h pair_all_sort_body.inc pair_tag.h collision_pairs.h breakup_pairs.h ../../include/sdm_hip.h ../../include/sdm_condensation.h ../../include/sdm_condensation_formulae.h ../../include/sdm_freezing.h ../../include/sdm_deposition.h ../../include/sdm_chemistry.h ../../include/sdm_seeding.h ../../include/sdm_relaxed_velocity.h ../../include/sdm_initialisation.h ../../include/sdm_parcel.h ../../include/sdm_parcel_diag.h ../../include/sdm_parcel_chem.h ../../include/sdm_parcel_vent.h ../../include/sdm_parcel_coal.h ../../include/sdm_parcel_breakup.h chemistry_rows.h toms748.h condensation_solver.h condensation_formulae.h parcel_solver.h; do
+  for dep in $f.hip common.h sdm_math.h sdm_math_tables.h physics.h index.h shuffle_device.h shuffle_build.h pair_all_sort_body.inc pair_tag.h collision_pairs.h breakup_pairs.h freezing_rows.h deposition_rows.h ../../include/sdm_parcel_ice.h ../../include/sdm_hip.h ../../include/sdm_condensation.h ../../include/sdm_condensation_formulae.h ../../include/sdm_freezing.h ../../include/sdm_deposition.h ../../include/sdm_chemistry.h ../../include/sdm_seeding.h ../../include/sdm_relaxed_velocity.h ../../include/sdm_initialisation.h ../../include/sdm_parcel.h ../../include/sdm_parcel_diag.h ../../include/sdm_parcel_chem.h ../../include/sdm_parcel_vent.h ../../include/sdm_parcel_coal.h ../../include/sdm_parcel_breakup.h chemistry_rows.h toms748.h condensation_solver.h condensation_formulae.h parcel_solver.h; do
     [ $stale = 1 ] || { [ $dep -nt $f.o ] && stale=1; } || true
   done
   if [ $stale = 1 ]; then

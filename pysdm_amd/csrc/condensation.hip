@@ -178,6 +178,11 @@ __global__ __launch_bounds__(COND_CB) void k_parcel_p(ParcelArgs<DefaultFormulae
                                                       ParcelPerm pp) {
   parcel_steps<DefaultFormulae, false, false, true>(a, nullptr, nullptr, &pp);
 }
+// include/sdm_parcel_ice.h: the step with the freezing and deposition passes after the solver
+__global__ __launch_bounds__(COND_CB) void k_parcel_i(ParcelArgs<DefaultFormulae> a,
+                                                      ParcelIce ic) {
+  parcel_steps<DefaultFormulae, false, false, false, true>(a, nullptr, nullptr, nullptr, &ic);
+}
 __global__ __launch_bounds__(COND_CB) void k_parcel_diagnose(
     ParcelDiagnoseArgs<DefaultFormulae> a) {
   parcel_diagnose_cells<DefaultFormulae>(a);
@@ -276,6 +281,19 @@ int sdm_parcel_launch_default_perm(sdm_ctx *ctx, const ParcelCall &call, const i
   const ParcelPerm pp{n_live, dv};
   hipLaunchKernelGGL(k_parcel_p, dim3((unsigned)call.n_parcel), dim3(COND_CB), 0, ctx->stream, a,
                      pp);
+  LAUNCH_CHECK();
+  return SDM_OK;
+}
+
+int sdm_parcel_launch_default_ice(sdm_ctx *ctx, const ParcelCall &call,
+                                  const ParcelIceCall &ice) {
+  ParcelArgs<DefaultFormulae> a;
+  SDM_PARCEL_FILL_ARGS(a, call);
+  a.c.k = consts_of(call.consts);
+  ARG_TRY(!call.requests);
+  const ParcelIce ic = parcel_ice_of(ice, call.cfg.dt);
+  hipLaunchKernelGGL(k_parcel_i, dim3((unsigned)call.n_parcel), dim3(COND_CB), 0, ctx->stream, a,
+                     ic);
   LAUNCH_CHECK();
   return SDM_OK;
 }

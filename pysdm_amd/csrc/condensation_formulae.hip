@@ -196,6 +196,11 @@ __global__ __launch_bounds__(COND_CB) void k_parcel_f_p(ParcelArgs<GeneralFormul
                                                         ParcelPerm pp) {
   parcel_steps<GeneralFormulae, false, false, true>(a, nullptr, nullptr, &pp);
 }
+// include/sdm_parcel_ice.h: the step with the freezing and deposition passes after the solver
+__global__ __launch_bounds__(COND_CB) void k_parcel_f_i(ParcelArgs<GeneralFormulae> a,
+                                                        ParcelIce ic) {
+  parcel_steps<GeneralFormulae, false, false, false, true>(a, nullptr, nullptr, nullptr, &ic);
+}
 // include/sdm_parcel_vent.h: the general formulae for a parcel whose air density and viscosity
 // change from step to step inside the kernel - the solver's cell scalars read the parcel's pair
 // from LDS (parcel_solver.h), everything else is GeneralFormulae's
@@ -331,6 +336,25 @@ int sdm_parcel_launch_general_perm(sdm_ctx *ctx, const ParcelCall &call,
   const ParcelPerm pp{n_live, dv};
   hipLaunchKernelGGL(k_parcel_f_p, dim3((unsigned)call.n_parcel), dim3(COND_CB), 0, ctx->stream,
                      a, pp);
+  LAUNCH_CHECK();
+  return SDM_OK;
+}
+
+int sdm_parcel_launch_general_ice(sdm_ctx *ctx, const ParcelCall &call,
+                                  const sdm_cond_formulae *formulae, const ParcelIceCall &ice) {
+  ParcelArgs<GeneralFormulae> a;
+  SDM_PARCEL_FILL_ARGS(a, call);
+  ARG_TRY(formulae && formulae_of(call.consts, formulae, &a.c.k.f));
+  ARG_TRY(formulae->option[SDM_COND_OPT_VENTILATION] == SDM_COND_VENT_NEGLECT);
+  ARG_TRY(formulae->option[SDM_COND_OPT_SURFACE_TENSION] == SDM_COND_SGM_CONSTANT || call.f_org);
+  ARG_TRY(!call.requests);
+  a.c.k.f_org = call.f_org;
+  a.c.k.reynolds_number = nullptr;
+  a.c.k.vdry = call.vdry;
+  a.c.k.air_density = a.c.k.air_dynamic_viscosity = nullptr;
+  const ParcelIce ic = parcel_ice_of(ice, call.cfg.dt);
+  hipLaunchKernelGGL(k_parcel_f_i, dim3((unsigned)call.n_parcel), dim3(COND_CB), 0, ctx->stream,
+                     a, ic);
   LAUNCH_CHECK();
   return SDM_OK;
 }

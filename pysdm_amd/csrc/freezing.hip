@@ -19,95 +19,11 @@
 // context's ready jumps, common.h), PCG_ELEMS consecutive draws.
 #include "common.h"
 #include "index.h"
-#include "../../include/sdm_freezing.h"
+#include "freezing_rows.h"
 
 #define GRID1D(n) dim3(grid_for(n)), dim3(SDM_BLOCK), 0, ctx->stream
 
 namespace {
-
-struct Kf {
-  double T0, rho_w, rho_i, eps, FWC_I[9], J_HET, ABIFM_M, ABIFM_C, ABIFM_UNIT, J_HOM, KOOP_2000[4],
-      KOOP_CORR, KOOP_UNIT, KOOP_MIN, KOOP_MAX, KOOP_MURRAY[7];
-};
-
-Kf consts_of(const double *c) {
-  Kf k;
-  k.T0 = c[SDM_FRZ_K_T0]; k.rho_w = c[SDM_FRZ_K_RHO_W]; k.rho_i = c[SDM_FRZ_K_RHO_I];
-  k.eps = c[SDM_FRZ_K_EPS];
-  for (int i = 0; i < 9; ++i) k.FWC_I[i] = c[SDM_FRZ_K_FWC_I0 + i];
-  k.J_HET = c[SDM_FRZ_K_J_HET]; k.ABIFM_M = c[SDM_FRZ_K_ABIFM_M];
-  k.ABIFM_C = c[SDM_FRZ_K_ABIFM_C]; k.ABIFM_UNIT = c[SDM_FRZ_K_ABIFM_UNIT];
-  k.J_HOM = c[SDM_FRZ_K_J_HOM];
-  for (int i = 0; i < 4; ++i) k.KOOP_2000[i] = c[SDM_FRZ_K_KOOP_2000_C1 + i];
-  k.KOOP_CORR = c[SDM_FRZ_K_KOOP_CORR]; k.KOOP_UNIT = c[SDM_FRZ_K_KOOP_UNIT];
-  k.KOOP_MIN = c[SDM_FRZ_K_KOOP_MIN_DA_W_ICE]; k.KOOP_MAX = c[SDM_FRZ_K_KOOP_MAX_DA_W_ICE];
-  for (int i = 0; i < 7; ++i) k.KOOP_MURRAY[i] = c[SDM_FRZ_K_KOOP_MURRAY_C0 + i];
-  return k;
-}
-
-// ---- formulae ------------------------------------------------------------------------------------
-// heterogeneous_ice_nucleation_rate/{constant,abifm}.py
-__device__ __forceinline__ double j_het(const Kf &k, int code, const double *a_w_ice, int64_t c) {
-  if (code == SDM_FRZ_JHET_CONSTANT) return k.J_HET;
-  return sdm_pow(10.0, k.ABIFM_M * (1 - a_w_ice[c]) + k.ABIFM_C) * k.ABIFM_UNIT;
-}
-
-// homogeneous_ice_nucleation_rate/{koop,koop_corr,koop_murray}.py
-__device__ __forceinline__ double j_hom(const Kf &k, int code, double T, double d) {
-  if (code == SDM_FRZ_JHOM_KOOPMURRAY2016) {
-    const double t = T - k.T0;
-    double s = k.KOOP_MURRAY[0] + k.KOOP_MURRAY[1] * t;
-    s = s + k.KOOP_MURRAY[2] * sdm_pow(t, 2.0);
-    s = s + k.KOOP_MURRAY[3] * sdm_pow(t, 3.0);
-    s = s + k.KOOP_MURRAY[4] * sdm_pow(t, 4.0);
-    s = s + k.KOOP_MURRAY[5] * sdm_pow(t, 5.0);
-    s = s + k.KOOP_MURRAY[6] * sdm_pow(t, 6.0);
-    return sdm_pow(10.0, s) * k.KOOP_UNIT;
-  }
-  double s = k.KOOP_2000[0] + k.KOOP_2000[1] * d;
-  s = s + k.KOOP_2000[2] * sdm_pow(d, 2.0);
-  s = s + k.KOOP_2000[3] * sdm_pow(d, 3.0);
-  if (code == SDM_FRZ_JHOM_KOOP_CORRECTION) s = s + k.KOOP_CORR;
-  return sdm_pow(10.0, s) * k.KOOP_UNIT;
-}
-
-// the immersion rate of cell c, NaN where no droplet of the cell can freeze (fm.py:99-103:
-// unfrozen_and_saturated needs RH > 1)
-__device__ __forceinline__ double het_rate_of_cell(const Kf &k, int code, const double *RH,
-                                                   const double *a_w_ice, int64_t c) {
-  if (!(RH[c] > 1)) return sdm_nan();
-  return j_het(k, code, a_w_ice, c);
-}
-
-// the homogeneous rate of cell c, NaN where no droplet of the cell can freeze (fm.py:149-160:
-// RH_ice > 1, d_a_w_ice within the formula's range, limited to its maximum)
-__device__ __forceinline__ double hom_rate_of_cell(const Kf &k, int code, const double *T,
-                                                   const double *RH_ice, const double *a_w_ice,
-                                                   int64_t c) {
-  const double rhi = RH_ice[c];
-  if (!(rhi > 1)) return sdm_nan();
-  if (code == SDM_FRZ_JHOM_CONSTANT) return k.J_HOM;  // constant.py: always in range
-  double d = (rhi - 1.0) * a_w_ice[c];
-  if (!(d >= k.KOOP_MIN)) return sdm_nan();
-  if (d > k.KOOP_MAX) d = k.KOOP_MAX;
-  return j_hom(k, code, T[c], d);
-}
-
-// fm.py:105-109 / :162-166 with trivia.py:158-163: true if the droplet freezes
-__device__ __forceinline__ bool nucleates(double rate_per_unit, double extent, double dt,
-                                          double u) {
-  const double r = rate_per_unit * extent;
-  const double prob = 1 - sdm_exp(-r * dt);
-  return u < prob;
-}
-
-// flatau_walko_cotton.py: pvs_ice
-__device__ __forceinline__ double pvs_ice(const Kf &k, double T) {
-  const double t = T - k.T0;
-  double s = k.FWC_I[7] + t * k.FWC_I[8];
-  for (int i = 6; i >= 0; --i) s = k.FWC_I[i] + t * s;
-  return s;
-}
 
 // ---- stage kernels ---------------------------------------------------------------------------------
 __global__ void k_freeze_singular(double *m_, const double *t_fz, const double *T,
@@ -117,12 +33,9 @@ __global__ void k_freeze_singular(double *m_, const double *t_fz, const double *
   if (i >= n) return;
   const double tfz = t_fz[i];
   if (tfz == 0) return;  // fm.py:52-53
-  const double m = m_[i];
+  double m = m_[i];
   const int64_t c = cell[i];
-  if (thaw && m < 0 && T[c] > T0)
-    m_[i] = -m;
-  else if (m > 0 && RH[c] > 1 && T[c] <= tfz)
-    m_[i] = -m;
+  if (freeze_singular_row(m, tfz, T[c], RH[c], thaw, T0)) m_[i] = m;
 }
 
 __global__ void k_freeze_time_dependent(const double *rand, double *m_, const double *area_,
@@ -133,12 +46,10 @@ __global__ void k_freeze_time_dependent(const double *rand, double *m_, const do
   if (i >= n) return;
   const double area = area_[i];
   if (area == 0) return;  // fm.py:92-93
-  const double m = m_[i];
+  double m = m_[i];
   const int64_t c = cell[i];
-  if (thaw && m < 0 && T[c] > k.T0)
-    m_[i] = -m;
-  else if (m > 0 && nucleates(het_rate_of_cell(k, code, RH, a_w_ice, c), area, dt, rand[i]))
-    m_[i] = -m;
+  const double rate = m > 0 ? het_rate_of_cell(k, code, RH, a_w_ice, c) : 0.0;  // (as read)
+  if (freeze_time_dependent_row(m, area, T[c], rate, dt, rand[i], thaw, k.T0)) m_[i] = m;
 }
 
 __global__ void k_freeze_time_dependent_homogeneous(const double *rand, double *m_,
@@ -148,27 +59,10 @@ __global__ void k_freeze_time_dependent_homogeneous(const double *rand, double *
                                                     int64_t n, int thaw, int code, Kf k) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const double m = m_[i];
+  double m = m_[i];
   const int64_t c = cell[i];
-  if (thaw && m < 0 && T[c] > k.T0)
-    m_[i] = -m;
-  else if (m > 0 &&
-           nucleates(hom_rate_of_cell(k, code, T, RH_ice, a_w_ice, c), volume[i], dt, rand[i]))
-    m_[i] = -m;
-}
-
-// fm.py:241-248; returns true if `data` changed
-__device__ __forceinline__ bool record_one(double &data, double m, double T_cell) {
-  if (m > 0) {
-    if (data > 0) {
-      data = sdm_nan();
-      return true;
-    }
-  } else if (data != data) {
-    data = T_cell;
-    return true;
-  }
-  return false;
+  const double rate = m > 0 ? hom_rate_of_cell(k, code, T, RH_ice, a_w_ice, c) : 0.0;  // (as read)
+  if (freeze_homogeneous_row(m, volume[i], T[c], rate, dt, rand[i], thaw, k.T0)) m_[i] = m;
 }
 
 __global__ void k_record_freezing_temperatures(double *data, const int64_t *cell_id,
@@ -183,11 +77,7 @@ __global__ void k_a_w_ice(const double *T, const double *p, const double *RH, co
                           double *a_w_ice, double *RH_ice, int64_t n, Kf k) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const double pvi = pvs_ice(k, T[i]);           // pm.py:87
-  const double pv = p[i] * qv[i] / (qv[i] + k.eps);  // libcloudphplusplus.py: pv
-  const double pvs = pv / RH[i];
-  a_w_ice[i] = pvi / pvs;
-  RH_ice[i] = pv / pvi;
+  a_w_ice_of(k, T[i], p[i], RH[i], qv[i], a_w_ice[i], RH_ice[i]);
 }
 
 // Python's max(0, x) / min(0, x) and numpy's maximum / minimum agree for every finite x and give
@@ -327,7 +217,7 @@ __global__ void __launch_bounds__(SDM_BLOCK) k_freezing_step(FrzArgs g) {
         const double rate = TABLE ? s_rate[g.n_cell + c]
                                   : hom_rate_of_cell(g.k, g.j_hom, g.T, g.RH_ice, g.a_w_ice, c);
         // (no column: mixed_phase_spheres.py mass_to_volume of this mass, which is > 0)
-        const double v = g.volume ? x[e] : m[e] / g.k.rho_w + 0.0 / g.k.rho_i;
+        const double v = g.volume ? x[e] : liquid_volume_of(g.k, m[e]);
         if (nucleates(rate, v, g.dt, u[e])) {
           m[e] = -m[e];
           changed[e] = !changed[e];
@@ -380,7 +270,7 @@ extern "C" int sdm_freeze_time_dependent(sdm_ctx *ctx, const double *rand,
   ARG_TRY(a_w_ice || j_het == SDM_FRZ_JHET_CONSTANT);
   hipLaunchKernelGGL(k_freeze_time_dependent, GRID1D(n_sd), rand, signed_water_mass,
                      immersed_surface_area, timestep, cell, a_w_ice, temperature,
-                     relative_humidity, n_sd, thaw, j_het, consts_of(consts));
+                     relative_humidity, n_sd, thaw, j_het, frz_consts_of(consts));
   LAUNCH_CHECK();
   return SDM_OK;
 }
@@ -396,7 +286,7 @@ extern "C" int sdm_freeze_time_dependent_homogeneous(
   ARG_TRY(a_w_ice || j_hom == SDM_FRZ_JHOM_CONSTANT);
   hipLaunchKernelGGL(k_freeze_time_dependent_homogeneous, GRID1D(n_sd), rand, signed_water_mass,
                      volume, timestep, cell, a_w_ice, temperature, relative_humidity_ice, n_sd,
-                     thaw, j_hom, consts_of(consts));
+                     thaw, j_hom, frz_consts_of(consts));
   LAUNCH_CHECK();
   return SDM_OK;
 }
@@ -421,7 +311,7 @@ extern "C" int sdm_a_w_ice(sdm_ctx *ctx, const double *T, const double *p, const
   if (n == 0) return SDM_OK;
   ARG_TRY(T && p && RH && water_vapour_mixing_ratio && a_w_ice && RH_ice);
   hipLaunchKernelGGL(k_a_w_ice, GRID1D(n), T, p, RH, water_vapour_mixing_ratio, a_w_ice, RH_ice,
-                     n, consts_of(consts));
+                     n, frz_consts_of(consts));
   LAUNCH_CHECK();
   return SDM_OK;
 }
@@ -487,7 +377,7 @@ extern "C" int sdm_freezing_step(sdm_ctx *ctx, const sdm_freezing_cfg *cfg, uint
   g.a_w_ice = a_w_ice;
   g.RH_ice = RH_ice;
   g.dt = cfg->timestep;
-  g.k = consts_of(consts);
+  g.k = frz_consts_of(consts);
   g.s_imm = g.s_hom = g.inc = 0;
   g.tab = ctx->pcg_tab;
   g.aff = ctx->pcg_aff;

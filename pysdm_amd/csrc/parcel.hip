@@ -7,6 +7,7 @@
 // memory once per call; k_parcel_d / k_parcel_f_d and k_parcel_diagnose(_f) read it there.
 // And include/sdm_parcel_vent.h: the same checks and chunking for formulae with a ventilation, on
 // k_parcel_v / k_parcel_v_d (condensation_formulae.hip).
+// And include/sdm_parcel_ice.h: the mixed-phase parcel, on k_parcel_i / k_parcel_f_i.
 //
 // A call of n_steps enqueues ceil(n_steps / steps_per_launch) launches back to back on the
 // context's stream, without synchronising between them: one launch stays short on a shared card,
@@ -227,6 +228,74 @@ extern "C" int sdm_parcel_run_vent(sdm_ctx *ctx, const sdm_parcel_cfg *cfg, int6
     call.k0 = k0;
     call.k_count = n_steps - k0 < per_launch ? n_steps - k0 : per_launch;
     const int launched = sdm_parcel_launch_vent(ctx, call, formulae, vent);
+    if (launched != SDM_OK) return launched;
+  }
+  return SDM_OK;
+}
+
+// include/sdm_parcel_ice.h: the same chunking on the kernels with the ice passes
+extern "C" int sdm_parcel_run_ice(sdm_ctx *ctx, const sdm_parcel_cfg *cfg,
+                                  const sdm_parcel_ice_cfg *ice_cfg, int64_t n_steps,
+                                  int64_t n_parcel, int64_t n_sd, const int64_t *parcel_start,
+                                  double *signed_water_mass, const int64_t *multiplicity,
+                                  const double *vdry, const double *kappa, const double *f_org,
+                                  double *v_cr, const sdm_parcel_state *state,
+                                  const double *w_mid, const sdm_parcel_profile *profile,
+                                  const double consts[34], const sdm_cond_formulae *formulae,
+                                  const sdm_parcel_ice_state *ice_state,
+                                  const sdm_parcel_ice_profile *ice_profile,
+                                  const double frz_consts[33], const double dep_consts[39]) {
+  ARG_TRY(ice_cfg && ice_state && frz_consts);
+  const bool freezing = ice_cfg->freezing != 0, deposition = ice_cfg->deposition != 0;
+  ARG_TRY(freezing || deposition);  // (neither: that is sdm_parcel_run)
+  ARG_TRY(ice_cfg->order == SDM_PARCEL_ICE_FREEZING_FIRST ||
+          ice_cfg->order == SDM_PARCEL_ICE_DEPOSITION_FIRST);
+  ARG_TRY(ice_state->a_w_ice && ice_state->RH_ice && ice_state->n_exceeded);
+  if (freezing) {
+    const bool immersion = ice_cfg->immersion_freezing != 0, singular = ice_cfg->singular != 0;
+    const bool hom = ice_cfg->homogeneous_freezing != 0;
+    if (immersion && !singular)
+      ARG_TRY(ice_cfg->j_het == SDM_FRZ_JHET_CONSTANT || ice_cfg->j_het == SDM_FRZ_JHET_ABIFM);
+    if (hom)
+      ARG_TRY(ice_cfg->j_hom >= SDM_FRZ_JHOM_CONSTANT &&
+              ice_cfg->j_hom <= SDM_FRZ_JHOM_KOOPMURRAY2016);
+    ARG_TRY(!(immersion && singular) || ice_state->freezing_temperature);
+    ARG_TRY(!(immersion && !singular) || ice_state->immersed_surface_area);
+    if ((immersion && !singular) || hom)
+      ARG_TRY(ice_state->rng_offset && ice_state->rng_state_inc);
+  }
+  if (deposition) {
+    ARG_TRY(dep_consts);
+    ARG_TRY(ice_cfg->coordinate == SDM_DEP_COORD_WATER_MASS_LOGARITHM ||
+            ice_cfg->coordinate == SDM_DEP_COORD_WATER_MASS);
+    ARG_TRY(ice_cfg->capacity == SDM_DEP_CAPACITY_SPHERICAL ||
+            ice_cfg->capacity == SDM_DEP_CAPACITY_COLUMNAR);
+    ARG_TRY(ice_cfg->kinetics == SDM_DEP_KINETICS_STANDARD ||
+            ice_cfg->kinetics == SDM_DEP_KINETICS_NEGLECT);
+    ARG_TRY(ice_cfg->sum == SDM_DEP_SUM_ORDERED || ice_cfg->sum == SDM_DEP_SUM_BLOCKED);
+  }
+  ParcelCall call;
+  bool with_diag, nothing_to_do;
+  // (a ventilation other than Neglect is refused there)
+  const int prepared = sdm_parcel_prepare(ctx, cfg, n_steps, n_parcel, n_sd, parcel_start,
+                                          signed_water_mass, multiplicity, vdry, kappa, f_org, v_cr,
+                                          state, w_mid, profile, consts, formulae, nullptr, nullptr,
+                                          &call, &with_diag, &nothing_to_do);
+  if (prepared != SDM_OK || nothing_to_do) return prepared;
+  ParcelIceCall ice;
+  ice.cfg = *ice_cfg;
+  ice.st = *ice_state;
+  if (ice_profile) ice.pr = *ice_profile;
+  else memset(&ice.pr, 0, sizeof(ice.pr));
+  ice.frz_consts = frz_consts;
+  ice.dep_consts = dep_consts;
+  const int64_t per_launch =
+      cfg->steps_per_launch > 0 ? cfg->steps_per_launch : SDM_PARCEL_STEPS_PER_LAUNCH;
+  for (int64_t k0 = 0; k0 < n_steps; k0 += per_launch) {
+    call.k0 = k0;
+    call.k_count = n_steps - k0 < per_launch ? n_steps - k0 : per_launch;
+    const int launched = formulae ? sdm_parcel_launch_general_ice(ctx, call, formulae, ice)
+                                  : sdm_parcel_launch_default_ice(ctx, call, ice);
     if (launched != SDM_OK) return launched;
   }
   return SDM_OK;

@@ -78,21 +78,8 @@ struct ParcelCoalArgs {
 struct PcoCollided { int32_t j, k; double g, u_b; };
 static_assert(sizeof(PcoCollided) == 24, "one record in the place of two rows of s0, s1, head");
 
-// the jump by `delta` draws of the LCG with increment `inc` as an affine map: state * m + p
-struct PcgAff { u128 m, p; };
-__device__ __forceinline__ PcgAff pcg_affine(u128 inc, uint64_t delta) {
-  u128 acc_mult = 1, acc_plus = 0, cur_mult = pcg_mult(), cur_plus = inc;
-  while (delta) {
-    if (delta & 1) {
-      acc_mult *= cur_mult;
-      acc_plus = acc_plus * cur_mult + cur_plus;
-    }
-    cur_plus = (cur_mult + 1) * cur_plus;
-    cur_mult *= cur_mult;
-    delta >>= 1;
-  }
-  return {acc_mult, acc_plus};
-}
+// (PcgAff, pcg_affine - the jump by `delta` draws as an affine map: parcel_solver.h, which the
+// mixed-phase parcel's kernels use too)
 
 // BREAKUP: the step of include/sdm_parcel_breakup.h with enable_breakup - a colliding pair bounces,
 // coalesces or breaks up.  The pair loop only LISTS the colliding pairs {j, k, gamma, u_b} in LDS

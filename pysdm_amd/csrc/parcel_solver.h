@@ -44,7 +44,10 @@
 #define SDM_PARCEL_SOLVER_H
 #include "condensation_solver.h"
 #include "physics.h"
+#include "freezing_rows.h"
+#include "deposition_rows.h"
 #include "../../include/sdm_parcel_vent.h"
+#include "../../include/sdm_parcel_ice.h"
 
 // one sdm_parcel_run call as the launchers take it (host struct; pointers are device pointers)
 struct ParcelCall {
@@ -103,6 +106,18 @@ int sdm_parcel_launch_vent(sdm_ctx *ctx, const ParcelCall &call,
 int sdm_parcel_diagnose_default(sdm_ctx *ctx, const ParcelDiagnoseCall &call);
 int sdm_parcel_diagnose_general(sdm_ctx *ctx, const ParcelDiagnoseCall &call,
                                 const sdm_cond_formulae *formulae);
+// the ice part of one sdm_parcel_run_ice call (include/sdm_parcel_ice.h; checked by the caller;
+// the constants of a pass that is switched off may be nullptr)
+struct ParcelIceCall {
+  sdm_parcel_ice_cfg cfg;
+  sdm_parcel_ice_state st;
+  sdm_parcel_ice_profile pr;
+  const double *frz_consts, *dep_consts;
+};
+// condensation.hip / condensation_formulae.hip: one launch of k_parcel_i / k_parcel_f_i
+int sdm_parcel_launch_default_ice(sdm_ctx *ctx, const ParcelCall &call, const ParcelIceCall &ice);
+int sdm_parcel_launch_general_ice(sdm_ctx *ctx, const ParcelCall &call,
+                                  const sdm_cond_formulae *formulae, const ParcelIceCall &ice);
 
 #ifdef __HIPCC__
 namespace {
@@ -326,15 +341,253 @@ struct ParcelPerm {
   double *dv;
 };
 
-template <class P, bool DIAG = false, bool VENT = false, bool PERM = false>
+// the jump by `delta` draws of the LCG with increment `inc` as an affine map: state * m + p (every
+// parcel has its own PCG64 increment, so the context's jump table - one increment - does not apply)
+struct PcgAff { u128 m, p; };
+__device__ __forceinline__ PcgAff pcg_affine(u128 inc, uint64_t delta) {
+  u128 acc_mult = 1, acc_plus = 0, cur_mult = pcg_mult(), cur_plus = inc;
+  while (delta) {
+    if (delta & 1) {
+      acc_mult *= cur_mult;
+      acc_plus = acc_plus * cur_mult + cur_plus;
+    }
+    cur_plus = (cur_mult + 1) * cur_plus;
+    cur_mult *= cur_mult;
+    delta >>= 1;
+  }
+  return {acc_mult, acc_plus};
+}
+
+// ---- ice (include/sdm_parcel_ice.h) ---------------------------------------------------------------
+// parcel_steps<P, false, false, false, true> (k_parcel_i, k_parcel_f_i) runs the freezing and
+// deposition passes in the step loop after cs.write_back() and before lane 0 overwrites s_par, so
+// the ascent stays one launch per steps_per_launch steps.  The row arithmetic is the text the stage
+// kernels compile (freezing_rows.h, deposition_rows.h).  What depends on the parcel only - the two
+// nucleation rates and the deposition's cell record - is formed once per parcel and step by lane 0
+// into LDS.  Position q of the parcel belongs to lane q % COND_CB in both passes, as in the solver:
+// a row is read once, carried through the passes in the order the call names and stored if it
+// changed.  The deposition's two sums ride the solver's LDS column, ICE_CH positions at a time
+// (first half dq, second half dth, a byte per position telling whether the row contributes), and
+// lane 0 adds them up in position order: serially (ORDERED, the reference's bits), or block by
+// block in the header's fixed tree shape (BLOCKED), carried out by lane 0 alone so that blocks may
+// span chunks.  The uniforms are the parcel's own PCG64 stream: a lane jumps to its first position
+// once per step (pcg_affine) and from there by COND_CB.  The carried pair (a_w_ice, RH_ice), the
+// stream position and the count of exceeded rows live in LDS between the steps; a failed step
+// leaves them as they were.
+#define ICE_CH (COND_CH / 2)
+struct ParcelIce {
+  int freezing, deposition, dep_first;
+  int imm_singular, imm_time_dependent, hom, thaw, j_het, j_hom, blocked;
+  sdm_parcel_ice_state st;
+  sdm_parcel_ice_profile pr;
+  Kf kf;
+  DepArgs dep;  // what dep_cell_record and dep_row read: k, coordinate, capacity, kinetics, dt
+};
+enum { PI_A_W_ICE, PI_RH_ICE, PI_NEW_A_W_ICE, PI_NEW_RH_ICE, PI_N };
+struct IceLds {
+  double pair[PI_N];
+  double T, p, RH;  // the current values, where the rate functions find them
+  double rate[2];   // immersion, homogeneous
+  double cv[DEP_CV];
+  double blk[2][SDM_DEP_SUM_BLOCK];
+  unsigned long long offset, n_exceeded, n_exceeded_step, n_ice;
+  unsigned char contributes[ICE_CH];
+};
+DF IceLds *ice_lds() {
+  __shared__ IceLds s_ice;
+  return &s_ice;
+}
+
+// the header's block reduction, by one lane
+DF double ice_block_sum(double *a, int len) {
+  for (int h = SDM_DEP_SUM_BLOCK / 2; h >= 1; h /= 2)
+    for (int j = 0; j < h; ++j)
+      if (j + h < len) a[j] += a[j + h];
+  return a[0];
+}
+
+// sdm_freezing_step for one row of a parcel (n_cell = 1, volume = NULL): the enabled passes in the
+// stage sequence's order, then the record of the temperature of last freezing; returns the mass.
+// `u_imm`, `u_hom`: the row's uniforms of the two stochastic passes
+DF double ice_freeze_row(const ParcelIce &ic, const IceLds *il, double m, int64_t row, double T,
+                         double RH, double dt, double u_imm, double u_hom) {
+  const int thaw = ic.thaw;
+  const double T0 = ic.kf.T0;
+  double mass = m;
+  if (ic.imm_singular) {
+    double x = mass;
+    if (freeze_singular_row(x, ic.st.freezing_temperature[row], T, RH, thaw, T0)) mass = x;
+  }
+  if (ic.imm_time_dependent) {
+    double x = mass;
+    if (freeze_time_dependent_row(x, ic.st.immersed_surface_area[row], T, il->rate[0], dt, u_imm,
+                                  thaw, T0))
+      mass = x;
+  }
+  if (ic.hom) {
+    double x = mass;
+    if (freeze_homogeneous_row(x, liquid_volume_of(ic.kf, mass), T, il->rate[1], dt, u_hom, thaw,
+                               T0))
+      mass = x;
+  }
+  if (ic.st.temperature_of_last_freezing) {
+    double data = ic.st.temperature_of_last_freezing[row];
+    if (record_one(data, mass, T)) ic.st.temperature_of_last_freezing[row] = data;
+  }
+  return mass;
+}
+
+// point 5 of the header for one parcel and step, and the sums of point 7.  Every lane of the
+// workgroup calls it; `pqv`, `pthd` (in: the solver's, out: with the deposition's additions),
+// `n_ice` and `ice_mass` are lane 0's.
+template <class P>
+DF void parcel_ice_passes(const ParcelIce &ic, IceLds *il, const CondArgs<P> &g, double *col,
+                          int64_t row0, int64_t n, int64_t c, int tid, double T, double p,
+                          double RH, double qv, double rhod, double thd, double dv, double dt,
+                          double &pqv, double &pthd, int64_t &n_ice, double &ice_mass) {
+  const bool stochastic = ic.freezing && (ic.imm_time_dependent || ic.hom);
+  if (tid == 0) {
+    il->T = T;
+    il->p = p;
+    il->RH = RH;
+    if (ic.freezing && ic.imm_time_dependent)
+      il->rate[0] = het_rate_of_cell(ic.kf, ic.j_het, &il->RH, &il->pair[PI_A_W_ICE], 0);
+    if (ic.freezing && ic.hom)
+      il->rate[1] = hom_rate_of_cell(ic.kf, ic.j_hom, &il->T, &il->pair[PI_RH_ICE],
+                                     &il->pair[PI_A_W_ICE], 0);
+    if (ic.deposition)
+      dep_cell_record(ic.dep, dv, T, p, RH, il->pair[PI_A_W_ICE], qv, rhod, thd, il->cv);
+    il->n_exceeded_step = 0;
+    il->n_ice = 0;
+  }
+  __syncthreads();
+  // the lane's generator at its first position of each stochastic pass
+  u128 st_imm = 0, st_hom = 0, inc = 0;
+  PcgAff over = {1, 0};
+  if (stochastic) {
+    const uint64_t *w = ic.st.rng_state_inc + 4 * c;
+    const u128 base = (((u128)w[0]) << 64) | w[1];
+    inc = (((u128)w[2]) << 64) | w[3];
+    const uint64_t off = (uint64_t)il->offset;
+    over = pcg_affine(inc, (uint64_t)COND_CB);
+    const PcgAff first = pcg_affine(inc, off + (uint64_t)tid);
+    st_imm = st_hom = base * first.m + first.p;
+    if (ic.imm_time_dependent && ic.hom) {
+      const PcgAff second = pcg_affine(inc, off + (uint64_t)n + (uint64_t)tid);
+      st_hom = base * second.m + second.p;
+    }
+  }
+  double accq = pqv, acct = pthd;  // (lane 0's)
+  int filled = 0;                  // entries of the open block (lane 0's, BLOCKED)
+  unsigned long long exceeded = 0, ice_count = 0;
+  double ice_part = 0.0;
+  for (int64_t base = 0; base < n; base += ICE_CH) {
+    const int len = (int)(n - base < ICE_CH ? n - base : ICE_CH);
+#pragma unroll
+    for (int s = 0; s < ICE_CH / COND_CB; ++s) {
+      const int slot = tid + s * COND_CB;
+      const int64_t q = base + slot;
+      double u_imm = 0, u_hom = 0;
+      if (stochastic) {  // (every lane advances by COND_CB positions, rows or not)
+        if (ic.imm_time_dependent) {
+          u_imm = pcg_output(st_imm * pcg_mult() + inc);
+          st_imm = st_imm * over.m + over.p;
+        }
+        if (ic.hom) {
+          u_hom = pcg_output(st_hom * pcg_mult() + inc);
+          st_hom = st_hom * over.m + over.p;
+        }
+      }
+      double dq = 0.0, dth = 0.0;
+      bool contributes = false;
+      if (q < n) {
+        const int64_t row = row0 + q;
+        const int64_t mult = g.multiplicity[row];
+        const double m_read = g.water_mass[row];
+        double m = m_read;
+        if (ic.freezing && !ic.dep_first)
+          m = ice_freeze_row(ic, il, m, row, T, RH, dt, u_imm, u_hom);
+        // sdm_deposition for one row (dm.py:42 `not unfrozen`: m > 0 is liquid; :79-80)
+        if (ic.deposition && !(m > 0) && !(il->cv[CV_S] == 1)) {
+          double m_new;
+          exceeded += dep_row(ic.dep, il->cv, m, mult, &m_new, &dq, &dth) ? 1 : 0;
+          m = m_new;
+          contributes = true;
+        }
+        if (ic.freezing && ic.dep_first)
+          m = ice_freeze_row(ic, il, m, row, T, RH, dt, u_imm, u_hom);
+        // (rows that do not change are not stored; a row the deposition evaluated is)
+        if (contributes || m != m_read) g.water_mass[row] = m;
+        if (m < 0) {
+          ice_count += (unsigned long long)mult;
+          ice_part += (double)mult * (-m);
+        }
+      }
+      col[slot] = dq;
+      col[ICE_CH + slot] = dth;
+      il->contributes[slot] = contributes ? 1 : 0;
+    }
+    if (ic.deposition) {  // (uniform)
+      __syncthreads();
+      if (tid == 0) {
+        for (int j = 0; j < len; ++j) {
+          if (!il->contributes[j]) continue;
+          if (!ic.blocked) {
+            accq += col[j];
+            acct += col[ICE_CH + j];
+            continue;
+          }
+          il->blk[0][filled] = col[j];
+          il->blk[1][filled] = col[ICE_CH + j];
+          if (++filled == SDM_DEP_SUM_BLOCK) {
+            accq += ice_block_sum(il->blk[0], filled);
+            acct += ice_block_sum(il->blk[1], filled);
+            filled = 0;
+          }
+        }
+      }
+      __syncthreads();
+    }
+  }
+  if (tid == 0 && filled > 0) {
+    accq += ice_block_sum(il->blk[0], filled);
+    acct += ice_block_sum(il->blk[1], filled);
+  }
+  // the SUM of sdm_parcel_diag.h of the lanes' partials; the two counts
+  if (exceeded) atomicAdd(&il->n_exceeded_step, exceeded);
+  if (ice_count) atomicAdd(&il->n_ice, ice_count);
+  col[tid] = ice_part;
+  __syncthreads();
+  if (tid < 64) {
+    const double *part = col + tid;
+    double sum = (part[0] + part[128]) + (part[64] + part[192]);  // strides 128, then 64
+#pragma unroll
+    for (int stride = 32; stride >= 1; stride >>= 1) sum += __shfl_down(sum, stride, 64);
+    if (tid == 0) {
+      ice_mass = sum;
+      n_ice = (int64_t)il->n_ice;
+      pqv = accq;
+      pthd = acct;
+      il->n_exceeded += il->n_exceeded_step;
+      if (stochastic)
+        il->offset += (unsigned long long)n * (unsigned long long)((ic.imm_time_dependent ? 1 : 0) +
+                                                                   (ic.hom ? 1 : 0));
+    }
+  }
+}
+
+template <class P, bool DIAG = false, bool VENT = false, bool PERM = false, bool ICE = false>
 DF void parcel_steps(const ParcelArgs<P> &a, const ParcelDiag *d = nullptr,
-                     const ParcelVent *v = nullptr, const ParcelPerm *pp = nullptr) {
+                     const ParcelVent *v = nullptr, const ParcelPerm *pp = nullptr,
+                     const ParcelIce *ic = nullptr) {
   __shared__ double s_par[PS_N];
   __shared__ int64_t s_nsub;
   DiagLds dl;
   if constexpr (DIAG) attach_diag_lds(dl);
   [[maybe_unused]] VentLds *vl = nullptr;
   if constexpr (VENT) vl = vent_lds();
+  [[maybe_unused]] IceLds *il = nullptr;
+  if constexpr (ICE) il = ice_lds();
   const CondArgs<P> &g = a.c;
   const typename P::K &k = g.k;
   const int tid = (int)threadIdx.x;
@@ -374,6 +627,12 @@ DF void parcel_steps(const ParcelArgs<P> &a, const ParcelDiag *d = nullptr,
         vl->air[PA_RHO] = v->air_density[c];
         vl->air[PA_ETA] = v->air_dynamic_viscosity[c];
         vl->out_of_range = 0;
+      }
+      if constexpr (ICE) {
+        il->pair[PI_A_W_ICE] = ic->st.a_w_ice[c];
+        il->pair[PI_RH_ICE] = ic->st.RH_ice[c];
+        il->offset = ic->st.rng_offset ? ic->st.rng_offset[c] : 0;
+        il->n_exceeded = 0;
       }
     }
     const double mass_of_dry_air = a.st.mass_of_dry_air[c];
@@ -439,13 +698,24 @@ DF void parcel_steps(const ParcelArgs<P> &a, const ParcelDiag *d = nullptr,
           }
         }
       }
-      // the critical volume of every row at the parcel's temperature; the copy of the masses the
-      // solver writes in place
+      if constexpr (ICE) {
+        // Moist.sync of this step (moist.py:73-100): the pair the NEXT step's ice passes read, from
+        // the advanced rhod and the thd and qv of before this step's condensation
+        if (tid == 0) {
+          double sync_T, sync_p, sync_RH;
+          P::tprh(k, prhod, thd, qv, sync_T, sync_p, sync_RH);
+          a_w_ice_of(ic->kf, sync_T, sync_p, sync_RH, qv, il->pair[PI_NEW_A_W_ICE],
+                     il->pair[PI_NEW_RH_ICE]);
+        }
+      }
+      // the critical volume of every row at the parcel's temperature (ICE: of every liquid row);
+      // the copy of the masses the solver writes in place
       for (int64_t q = tid; q < n; q += COND_CB) {
         const int64_t row = row_at(q);
         if (PERM && row < 0) continue;
         const double m = g.water_mass[row];
-        a.v_cr[row] = P::critical_volume(k, row, g.kappa[row], g.vdry[row], m / P::rho_w(k), T);
+        if (!ICE || m > 0)
+          a.v_cr[row] = P::critical_volume(k, row, g.kappa[row], g.vdry[row], m / P::rho_w(k), T);
         if (q >= COND_CH) a.mass_backup[row] = m;
         if constexpr (VENT) {  // attributes/physics/reynolds_number.py of the mass before the step
           const double r = radius_of_volume(volume_of_mass(m, P::rho_w(k)), 1 / P::pi_4_3(k));
@@ -465,10 +735,29 @@ DF void parcel_steps(const ParcelArgs<P> &a, const ParcelDiag *d = nullptr,
       }
       cs.write_back();
       done += 1;
+      double pthd = s.o.thd, pqv = s.o.qv;  // (with the deposition's additions: lane 0's)
+      [[maybe_unused]] int64_t n_ice = 0;
+      [[maybe_unused]] double ice_mass = 0;
+      [[maybe_unused]] double nT_ice = 0, np_ice = 0, nRH_ice = 0;
+      if constexpr (ICE) {
+        // T, p, RH of the state after the condensation alone: the deposition leaves them stale
+        // (include/sdm_parcel_ice.h, point 6)
+        if (tid == 0) P::tprh(k, prhod, pthd, pqv, nT_ice, np_ice, nRH_ice);
+        // the passes read the state of before the step: every lane's p and RH before lane 0
+        // overwrites s_par (the passes end with barriers)
+        parcel_ice_passes<P>(*ic, il, g, cs.col, row0, n, c, tid, T, s_par[PS_P], s_par[PS_RH], qv,
+                             rhod, thd, dv, a.dt, pqv, pthd, n_ice, ice_mass);
+      }
       if (tid == 0) {
         const double new_rhod = s_par[PS_PRHOD];
         double nT, np, nRH;
-        P::tprh(k, new_rhod, s.o.thd, s.o.qv, nT, np, nRH);
+        if constexpr (ICE) {
+          nT = nT_ice;
+          np = np_ice;
+          nRH = nRH_ice;
+        } else {
+          P::tprh(k, new_rhod, pthd, pqv, nT, np, nRH);
+        }
         int64_t ns = s.n;
         if (g.adaptive) {  // dynamics/condensation.py:122-131
           ns = ns > a.n_clamp_lo ? ns : a.n_clamp_lo;
@@ -477,8 +766,8 @@ DF void parcel_steps(const ParcelArgs<P> &a, const ParcelDiag *d = nullptr,
         s_par[PS_QV_PREV] = s_par[PS_QV];
         s_par[PS_Z] = s_par[PS_PZ];
         s_par[PS_RHOD] = new_rhod;
-        s_par[PS_THD] = s.o.thd;
-        s_par[PS_QV] = s.o.qv;
+        s_par[PS_THD] = pthd;
+        s_par[PS_QV] = pqv;
         s_par[PS_T] = nT;
         s_par[PS_P] = np;
         s_par[PS_RH] = nRH;
@@ -495,8 +784,18 @@ DF void parcel_steps(const ParcelArgs<P> &a, const ParcelDiag *d = nullptr,
         const int64_t at = (a.k0 + j) * a.n_parcel + c;
         if (a.pr.z) a.pr.z[at] = s_par[PS_Z];
         if (a.pr.rhod) a.pr.rhod[at] = new_rhod;
-        if (a.pr.thd) a.pr.thd[at] = s.o.thd;
-        if (a.pr.qv) a.pr.qv[at] = s.o.qv;
+        if (a.pr.thd) a.pr.thd[at] = pthd;
+        if (a.pr.qv) a.pr.qv[at] = pqv;
+        if constexpr (ICE) {
+          il->pair[PI_A_W_ICE] = il->pair[PI_NEW_A_W_ICE];
+          il->pair[PI_RH_ICE] = il->pair[PI_NEW_RH_ICE];
+          if (ic->pr.a_w_ice) ic->pr.a_w_ice[at] = il->pair[PI_A_W_ICE];
+          if (ic->pr.RH_ice) ic->pr.RH_ice[at] = il->pair[PI_RH_ICE];
+          if (ic->pr.n_ice) ic->pr.n_ice[at] = n_ice;
+          if (ic->pr.ice_mass) ic->pr.ice_mass[at] = ice_mass;
+          if (ic->pr.n_exceeded) ic->pr.n_exceeded[at] = (int64_t)il->n_exceeded_step;
+          if (ic->pr.dv) ic->pr.dv[at] = dv;
+        }
         if (a.pr.T) a.pr.T[at] = nT;
         if (a.pr.p) a.pr.p[at] = np;
         if (a.pr.RH) a.pr.RH[at] = nRH;
@@ -534,8 +833,42 @@ DF void parcel_steps(const ParcelArgs<P> &a, const ParcelDiag *d = nullptr,
         v->air_dynamic_viscosity[c] = vl->air[PA_ETA];
         if (out_of_table && v->out_of_table) v->out_of_table[c] = 1;
       }
+      if constexpr (ICE) {  // (a failed step left all of it as it was)
+        ic->st.a_w_ice[c] = il->pair[PI_A_W_ICE];
+        ic->st.RH_ice[c] = il->pair[PI_RH_ICE];
+        if (ic->st.rng_offset) ic->st.rng_offset[c] = (uint64_t)il->offset;
+        ic->st.n_exceeded[c] += (int64_t)il->n_exceeded;
+      }
     }
   }
+}
+
+// what both ice launchers do with a ParcelIceCall: the kernels' ParcelIce
+inline ParcelIce parcel_ice_of(const ParcelIceCall &ice, double dt) {
+  ParcelIce ic;
+  memset(&ic, 0, sizeof(ic));
+  const sdm_parcel_ice_cfg &cfg = ice.cfg;
+  ic.freezing = cfg.freezing != 0;
+  ic.deposition = cfg.deposition != 0;
+  ic.dep_first = cfg.order == SDM_PARCEL_ICE_DEPOSITION_FIRST;
+  ic.imm_singular = cfg.immersion_freezing && cfg.singular;
+  ic.imm_time_dependent = cfg.immersion_freezing && !cfg.singular;
+  ic.hom = cfg.homogeneous_freezing != 0;
+  ic.thaw = cfg.thaw != 0;
+  ic.j_het = cfg.j_het;
+  ic.j_hom = cfg.j_hom;
+  ic.blocked = cfg.sum == SDM_DEP_SUM_BLOCKED;
+  ic.st = ice.st;
+  ic.pr = ice.pr;
+  // (Moist.sync's a_w_ice reads T0, eps and the ice saturation polynomial of the freezing
+  // constants also where only the deposition is switched on)
+  ic.kf = frz_consts_of(ice.frz_consts);
+  if (ic.deposition) ic.dep.k = dep_consts_of(ice.dep_consts);
+  ic.dep.coordinate = cfg.coordinate;
+  ic.dep.capacity = cfg.capacity;
+  ic.dep.kinetics = cfg.kinetics;
+  ic.dep.dt = dt;
+  return ic;
 }
 
 }  // namespace

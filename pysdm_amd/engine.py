@@ -49,6 +49,8 @@ class Engine:
     parcel_coal_library = None
     # likewise include/sdm_parcel_breakup.h
     parcel_breakup_library = None
+    # likewise include/sdm_parcel_ice.h
+    parcel_ice_library = None
     # whether the fused collision step of `library` can take the fall velocity from the
     # "relative fall momentum" row; an engine that cannot must refuse, not ignore the request
     fused_momentum_velocity = False
@@ -198,6 +200,14 @@ class Engine:
         self._before_call()
         self.parcel_breakup_library.invoke(symbol, self.handle, args)
 
+    def call_parcel_ice(self, symbol, *args):
+        """a symbol of include/sdm_parcel_ice.h"""
+        if self.parcel_ice_library is None:
+            raise NotImplementedError(
+                f"engine `{self.name}` has no library for the mixed-phase parcel")
+        self._before_call()
+        self.parcel_ice_library.invoke(symbol, self.handle, args)
+
     def _before_call(self):
         pass
 
@@ -240,6 +250,7 @@ class HipEngine(Engine):
         self.parcel_vent_library = abi.parcel_vent_library()
         self.parcel_coal_library = abi.parcel_coal_library()
         self.parcel_breakup_library = abi.parcel_breakup_library()
+        self.parcel_ice_library = abi.parcel_ice_library()
         self.handle = abi.c_ptr()
         self.library.check(self.library.cdll.sdm_ctx_create(ctypes.byref(self.handle),
                                                             abi.c_int(device_index)))

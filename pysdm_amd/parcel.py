@@ -36,6 +36,7 @@ import numpy as np
 
 from . import abi
 from . import chemistry as chem
+from . import parcel_ice
 from . import terminal_velocity as tv
 from .condensation import (CONSTANT_NAMES, OPTION_ORDER, _option_name, check_formulae,
                            condensation_call, critical_volume_call, is_default,
@@ -443,7 +444,8 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
                  steps_per_launch=0, general=False, chemistry=None, mole_fractions=None,
                  dry_rho=None, dry_molar_mass=None, initial_moles=None, molar_mass=None,
                  terminal_velocity=None, descriptor=None, collisions=None, seed=None,
-                 breakup=False):
+                 breakup=False, freezing=None, deposition=None, ice_order="freezing_first",
+                 ice_seed=None, freezing_temperature=None, immersed_surface_area=None):
         """`terminal_velocity`: a name or a law object of pysdm_amd.terminal_velocity, needed
         (and read) with a ventilation other than Neglect, and by the collision kernels that take
         a fall velocity (the Gunn-Kinzer table if not given).  `descriptor`: one of
@@ -453,11 +455,25 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
         setup's), each parcel drawing from its own NumPy-PCG64 stream.  `breakup=True`: the
         third dynamic is `Collision` / `Breakup` (include/sdm_parcel_breakup.h) - `collisions` may
         then be a set-up with breakup (CollisionSetup.collision, .breakup_only; without the keyword
-        such a set-up is refused); a set-up of coalescence runs as it does without the keyword"""
+        such a set-up is refused); a set-up of coalescence runs as it does without the keyword.
+        `freezing` (a `freezing.FreezingSetup`) and / or `deposition` (True, or a dict with `sum`:
+        "ordered" / "blocked"): the mixed-phase parcel (include/sdm_parcel_ice.h, pysdm_amd/
+        parcel_ice.py) - `formulae` then name MixedPhaseSpheres, `water_mass` is the signed water
+        mass, `ice_order` is "freezing_first" or "deposition_first", `ice_seed` an int or one per
+        parcel (default: the formulae's), `freezing_temperature` / `immersed_surface_area` the
+        per-row columns the set-up reads; `run` then returns (profile, ice profile)"""
         if route not in ROUTES:
             raise ValueError(f"route must be one of {ROUTES}, not {route!r}")
         check_hydrostatics(formulae)
         self.engine, self.formulae, self.setup = engine, formulae, setup
+        self.mixed_phase = freezing is not None or bool(deposition)
+        if self.mixed_phase:
+            if descriptor is not None or chemistry is not None or collisions is not None:
+                raise NotImplementedError(
+                    "mixed-phase parcel: no descriptor=, chemistry or collisions in the same run")
+            descriptor = parcel_ice.descriptor(formulae)
+            if descriptor.option[_VENT] != 0 or terminal_velocity is not None:
+                raise NotImplementedError("mixed-phase parcel: ventilated ice is not served")
         self.descriptor = check_formulae(formulae) if descriptor is None else descriptor
         self.ventilated = self.descriptor.option[_VENT] != 0
         self.terminal_velocity = None
@@ -505,6 +521,7 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
         if collisions is not None:
             self._check_collisions(collisions, route, counts)
         self.route, self.general = route, bool(general)
+        self.ice = None
         self.dt = float(dt)
         self.cfg = parcel_cfg(formulae, setup, self.dt, steps_per_launch)
         counts = np.asarray(counts, dtype=np.int64).reshape(-1)
@@ -549,7 +566,7 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
         }
         temperature_pressure_rh_call(engine, formulae, self.state["rhod"], self.state["thd"],
                                      self.state["qv"], self.state["T"], self.state["p"],
-                                     self.state["RH"], n_parcel)
+                                     self.state["RH"], n_parcel, mixed_phase=self.mixed_phase)
         self.parcel_start = up(self.parcel_start_host)
         self.multiplicity = column(multiplicity, "multiplicity", np.int64)
         self.water_mass = column(water_mass, "water_mass", float)
@@ -565,6 +582,11 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
             self.reynolds_number = engine.full(n_sd, FLOAT, np.nan)
             self.out_of_table = engine.zeros(n_parcel, INT)
             self._vent_law = vent_law(engine, self.terminal_velocity)
+        if self.mixed_phase:
+            self.ice = parcel_ice.IceParcel(
+                self, freezing=freezing, deposition=deposition, order=ice_order, seed=ice_seed,
+                freezing_temperature=freezing_temperature,
+                immersed_surface_area=immersed_surface_area)
         if chemistry is not None:
             self._init_chemistry(mole_fractions, dry_rho, dry_molar_mass, initial_moles,
                                  molar_mass, np.ascontiguousarray(dry_volume, dtype=float),
@@ -575,6 +597,7 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
                                   np.broadcast_to(np.asarray(kappa, dtype=float), (n_sd,)))
         self.last_chem_profile = None
         self.last_coal_profile = None
+        self.last_ice_profile = None
         self.n_steps = 0  # time steps asked for so far: the clock of w(t)
         self.last_profile = None
         self.last_products = None
@@ -1101,7 +1124,16 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
                 record = {name: eng.full(n_steps * n_parcel, INT, -1) if name.startswith("n_")
                           else eng.full(n_steps * n_parcel, FLOAT, np.nan)
                           for name in abi.PARCEL_PROFILE_FIELDS}
-            if self.route == "fused":
+            if self.ice is not None:
+                if table is not None:
+                    raise NotImplementedError(
+                        "mixed-phase parcel: the only products are those of the ice profile")
+                ice_record = self.ice.record(eng, n_steps * n_parcel)
+                if self.route == "fused":
+                    self.ice.run_fused(self, n_steps, w_mid, record, ice_record)
+                else:
+                    self.ice.run_stages(self, w_mid, record, ice_record)
+            elif self.route == "fused":
                 parcel_call(eng, self.formulae, self.cfg, n_steps=n_steps,
                             parcel_start=self.parcel_start, water_mass=self.water_mass,
                             multiplicity=self.multiplicity, dry_volume=self.dry_volume,
@@ -1156,6 +1188,12 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
                         for name, array in coal_record.items()}
             self.last_coal_profile = coal_out
             self._coal_warnings()
+        ice_out = None
+        if self.ice is not None:
+            if n_steps > 0:
+                ice_out = {name: eng.download(array).reshape(n_steps, n_parcel)
+                           for name, array in ice_record.items()}
+            self.last_ice_profile = ice_out
         failed = eng.download(self.state["failed_step"])
         for parcel in np.flatnonzero(failed >= 0):
             if int(parcel) not in self._reported:
@@ -1167,6 +1205,8 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
             return (out, chem_out) if table is None else (out, chem_out, values)
         if self.collisions is not None:
             return out, coal_out
+        if self.ice is not None:
+            return out, ice_out
         return out if table is None else (out, values)
 
     # ---- ventilation (include/sdm_parcel_vent.h) ---------------------------------------------------
@@ -1419,6 +1459,8 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
             out["out_of_table"] = down(self.out_of_table)
         if self.chemistry is not None:
             out.update(self._chem_columns(down))
+        if self.ice is not None:  # (the carried pair is among the state arrays)
+            out.update(self.ice.columns(down))
         if self.collisions is not None:
             out.update(self._coal_columns(down))
             # (positions past a parcel's live ones hold nothing that is defined)
@@ -1454,6 +1496,8 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
                                out_of_table=self.out_of_table)
             if self.chemistry is not None:
                 columns.update(self._chem_columns())
+            if self.ice is not None:
+                columns.update(self.ice.columns())
             if self.collisions is not None:
                 columns.update(self._coal_columns())
                 if name in ("idx", "n_live"):
@@ -1469,6 +1513,7 @@ class ParcelRunner:  # pylint: disable=too-many-instance-attributes
         if {"rhod", "thd", "qv"} & set(state) and not {"T", "p", "RH"} & set(state):
             temperature_pressure_rh_call(eng, self.formulae, self.state["rhod"],
                                          self.state["thd"], self.state["qv"], self.state["T"],
-                                         self.state["p"], self.state["RH"], self.n_parcel)
+                                         self.state["p"], self.state["RH"], self.n_parcel,
+                                         mixed_phase=self.mixed_phase)
         failed = eng.download(self.state["failed_step"])
         self._reported = {int(p) for p in np.flatnonzero(failed >= 0)}

@@ -54,6 +54,16 @@ on the fused route (`sdm_parcel_run_collision`) against the stage route (the sta
 `sdm_collision_step` with breakup, parcel by parcel) and against the same ascents with
 coalescence only.  Writes profiles/parcel_breakup_timing.json with the ratios; the one claim is
 that fused is not slower than stages.
+
+`python scripts/bench_parcel.py --ice` times the mixed-phase parcel (include/sdm_parcel_ice.h;
+tests/parcel_ice_cases.py's cold ensemble: 1024 parcels of 256 rows, a quarter of them ice, 20
+steps of 0.1 s, time-dependent immersion freezing and homogeneous freezing with constant rates,
+then deposition, ordered sums): `sdm_parcel_run_ice`, `sdm_parcel_run` alone on the same rows (the
+solver leaves the ice alone) and the stage route (parcel by parcel with read-backs; one call).
+With `--against DIR` (a checkout of the parent commit with its own library built) it then runs the
+default measurement of this script - the four parcel counts, both formulae, fused route - there
+and here, alternating, `--rounds` times, each in a process of its own, to show that the existing
+kernels did not move.  Writes profiles/parcel_ice_timing.json with the ratios; no threshold.
 """
 import argparse
 import json
@@ -481,6 +491,98 @@ def main_breakup(args):
     print("wrote", out)
 
 
+ICE_PARCELS, ICE_STEPS = 1024, 20
+
+
+def measure_ice(mode, n_parcel, reps, warmup, engine=None, time_it=timed):
+    """`mode`: "fused" (sdm_parcel_run_ice), "stages" (the chain of stage symbols) or
+    "condensation only" (sdm_parcel_run on the same rows)"""
+    from pysdm_amd.condensation import CondensationSetup  # pylint: disable=import-outside-toplevel
+    from pysdm_amd.engine import HipEngine  # pylint: disable=import-outside-toplevel
+    from pysdm_amd.formulae import Formulae  # pylint: disable=import-outside-toplevel
+    from pysdm_amd.parcel import ParcelRunner  # pylint: disable=import-outside-toplevel
+    from tests import parcel_cases as pc  # pylint: disable=import-outside-toplevel
+    from tests import parcel_ice_cases as ic  # pylint: disable=import-outside-toplevel
+
+    engine = engine or HipEngine.get()
+    kwargs = ic.ensemble((N_SD,) * n_parcel, seed=3, mode="both")
+    if mode == "condensation only":
+        formulae = Formulae()
+        plain = {key: value for key, value in kwargs.items() if key not in (
+            "freezing_temperature", "immersed_surface_area", "ice_seed")}
+        runner = ParcelRunner(engine, formulae, CondensationSetup(), route="fused",
+                              **pc.saturated(plain, formulae))
+        call = None
+    else:
+        runner = ic.runner(engine, kwargs, mode, mode="both")
+        call = lambda r, steps: r.run(steps, profile=False)  # noqa: E731
+    start = runner.snapshot()
+    samples = time_it(runner, start, ICE_STEPS, reps, warmup, call)
+    final = runner.snapshot()
+    assert (final["failed_step"] == -1).all() and (final["steps_done"] == ICE_STEPS).all()
+    ms = float(np.median(samples))
+    out = {"mode": mode, "n_parcel": n_parcel, "n_sd_per_parcel": N_SD, "steps": ICE_STEPS,
+           "reps": reps, "ms_median": round(ms, 3), "ms_min": round(float(np.min(samples)), 3),
+           "ms_max": round(float(np.max(samples)), 3),
+           "ms_per_parcel_step": round(ms / (n_parcel * ICE_STEPS), 5)}
+    if mode != "condensation only":
+        out["frozen_fraction"] = round(ic.frozen_fraction(kwargs, final), 3)
+        out["n_exceeded"] = int(final["n_exceeded"].sum())
+    return out
+
+
+def default_line_against(parent_root, rounds):
+    """the default measurement (fused route, the four parcel counts, both formulae) in the parent's
+    tree and in this one, alternating, each run a process of its own; ms_median per run"""
+    import subprocess  # pylint: disable=import-outside-toplevel
+    import tempfile  # pylint: disable=import-outside-toplevel
+
+    runs = []
+    for round_ in range(rounds):
+        for which, root in (("parent", os.path.abspath(parent_root)), ("this commit", ROOT)):
+            with tempfile.NamedTemporaryFile(suffix=".json") as handle:
+                subprocess.run([sys.executable, os.path.join(root, "scripts", "bench_parcel.py"),
+                                "--out", handle.name], cwd=root, check=True,
+                               stdout=subprocess.DEVNULL, timeout=300)
+                with open(handle.name, encoding="utf-8") as result:
+                    rows = json.load(result)["results"]
+            runs.append({"round": round_, "tree": which, "ms_median": {
+                f"{r['formulae']}, {r['n_parcel']} parcels": r["ms_median"]
+                for r in rows if r["route"] == "fused"}})
+            print(json.dumps(runs[-1]), flush=True)
+    return runs
+
+
+def main_ice(args):
+    results = []
+    for mode in ("condensation only", "fused", "stages"):
+        # (the stage route: tens of seconds per call at this shape; one call, no warm-up)
+        reps, warmup = (1, 0) if mode == "stages" else (args.reps, args.warmup)
+        results.append(measure_ice(mode, ICE_PARCELS, reps, warmup))
+        print(json.dumps(results[-1]), flush=True)
+    by = {r["mode"]: r for r in results}
+    ratios = {"stages / fused": round(by["stages"]["ms_median"] / by["fused"]["ms_median"], 1),
+              "fused / condensation only":
+                  round(by["fused"]["ms_median"] / by["condensation only"]["ms_median"], 3)}
+    against = "not measured"
+    if args.against:
+        against = default_line_against(args.against, args.rounds)
+    out = args.out or os.path.join(ROOT, "profiles", "parcel_ice_timing.json")
+    with open(out, "w", encoding="utf-8") as handle:
+        handle.write(json.dumps({
+            "workload": f"{N_SD} rows per parcel, a quarter ice, {ICE_STEPS} steps of 0.1 s at 255 "
+                        "- 262 K, water-saturated ascents; Freezing(singular=False, "
+                        "homogeneous_freezing=True) with constant rates, then "
+                        "VapourDepositionOnIce, ordered sums; HIP events, median of "
+                        f"{args.reps} after {args.warmup} warm-up call(s); the stage route: one "
+                        "call",
+            "results": results, "ratios": ratios,
+            "default measurement, this commit against the parent, alternating": against},
+            indent=1) + "\n")
+    print(json.dumps(ratios))
+    print("wrote", out)
+
+
 def main():
     parser = argparse.ArgumentParser()
     parser.add_argument("--reps", type=int, default=5)
@@ -500,7 +602,16 @@ def main():
                         help="time the parcel with coalescence instead (see the docstring)")
     parser.add_argument("--breakup", action="store_true",
                         help="time the parcel with collisional breakup instead (see the docstring)")
+    parser.add_argument("--ice", action="store_true",
+                        help="time the mixed-phase parcel instead (see the docstring)")
+    parser.add_argument("--against", default=None,
+                        help="with --ice: a checkout of the parent commit (library built) to run "
+                             "the default measurement against, alternating")
+    parser.add_argument("--rounds", type=int, default=2)
     args = parser.parse_args()
+    if args.ice:
+        main_ice(args)
+        return
     if args.breakup:
         main_breakup(args)
         return
